@@ -3,9 +3,18 @@
 GB/s on MI355X.  One JSON line on rank 0.
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--workload C3|C5]
+                    [--dump-outputs DIR] [--full]
 
 A step = one full projected-BB iteration (python/BB.py:17-41 semantics, fused
 K2 -> K3 -> K1 on the device) over the whole problem, inputs resident in HBM.
+
+A plain run does what the headline needs and no more: it builds the workload,
+runs W untimed steps, times exactly K steps in one window, writes the outputs
+of the last timed step where --dump-outputs asks for them, and prints the
+line (metric, value, unit, higher_is_better, dtype, ms_per_step, the
+config).  Everything else described below -- the per-kernel table and its
+roofline, the ten-window spread, the C5 leg, the N = 1 legs of the other
+paths, the CPU baselines and the one-rank RCCL self-check -- runs with --full.
 
 Headline (BASELINE.json's metric and configs[2]): C3, 1M routes / 50k blocks /
 100k links / 16M nnz.  At N = 1 `value` is C3's iterations/s on one GPU.  At
@@ -732,6 +741,34 @@ def time_run(run, steps, warmup, dist, windows=1):
     return els
 
 
+DUMP_BYTES = 64 * 2 ** 20      # --dump-outputs: at most this much in all
+DUMP_SEED = 237423433
+
+
+def dump_outputs(dirname, arrays, budget=DUMP_BYTES):
+    """--dump-outputs: each of `arrays` (name -> device tensor or ndarray) as
+    dirname/<name>.npy in float64.  Within `budget` bytes in all every array
+    is written whole; beyond it each keeps the same share of its entries, at
+    indices drawn once from RandomState(DUMP_SEED) over its length (sorted, so
+    the same entries on every run and build).  Returns name -> entries kept."""
+    os.makedirs(dirname, exist_ok=True)
+    host = {}
+    for name, a in arrays.items():
+        a = a.detach().cpu().numpy() if hasattr(a, 'detach') else np.asarray(a)
+        host[name] = np.ascontiguousarray(a, dtype=np.float64).reshape(-1)
+    total = sum(a.nbytes for a in host.values())
+    kept = {}
+    for name, a in host.items():
+        if total > budget:
+            # (.npy headers are 128 bytes each: the shares leave room for them)
+            k = int(a.size * (budget - 1024 * len(host)) // total)
+            if k < a.size:
+                a = a[np.sort(np.random.RandomState(DUMP_SEED).choice(a.size, k, replace=False))]
+        np.save(os.path.join(dirname, name + '.npy'), a)
+        kept[name] = int(a.size)
+    return kept
+
+
 def kernel_table(eng, it0, reps, world, m, n, nz, p, nnz):
     """Per-kernel HIP-event timing on the stream the kernels run on: each stage
     launched `reps` times back to back between two events (the stages are
@@ -988,13 +1025,22 @@ def main():
     ap.add_argument('--legs', default='all',
                     help='comma list of %s (N = 1; default all): one rocprofv3 run per leg '
                          'keeps each workload\'s kernel rows apart' % ','.join(LEGS))
-    ap.add_argument('--profile-iters', type=int, default=20)
+    ap.add_argument('--full', action='store_true',
+                    help='everything beside the headline: the per-kernel table and roofline, '
+                         '10 timed windows, the C5 leg, the N = 1 legs (--legs), the CPU '
+                         'baselines and the one-rank RCCL self-check')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='after the timed steps, write what the last one left (z, x, r and the '
+                         'loop\'s scalars of rank 0) as DIR/<name>.npy, float64, at most 64 MB')
+    ap.add_argument('--profile-iters', type=int, default=None,
+                    help='launches per stage of the per-kernel table (--full; default 20)')
     ap.add_argument('--model-exchange', default=None,
                     help='US_PER_MB[,FIXED_US]: with --rehearse-shard, model every exchange '
                          'as a spin of that cost on its stream (timing only)')
-    ap.add_argument('--windows', type=int, default=10,
+    ap.add_argument('--windows', type=int, default=None,
                     help='timed windows of --steps iterations each; the line reports the '
-                         'median window and the spread')
+                         'median window and the spread (default: 1, so that --steps is the '
+                         'number of timed steps; 10 with --full)')
     ap.add_argument('--rehearse-shard', type=int, default=0,
                     help='one GPU, one process: time rank 0 of an N-way C5 partition through '
                          'the sharded (RCCL) driver -- per-rank cost without the fabric')
@@ -1006,6 +1052,15 @@ def main():
     legs = set(LEGS) if args.legs == 'all' else set(args.legs.split(','))
     if legs - set(LEGS):
         raise SystemExit('unknown legs %s' % sorted(legs - set(LEGS)))
+    if not args.full:
+        # a plain run: the headline alone, --steps timed steps in one window
+        if args.legs != 'all' and legs != {'main'}:
+            ap.error('--legs %s needs --full' % args.legs)
+        legs = {'main'}
+    if args.windows is None:
+        args.windows = 10 if args.full else 1
+    if args.profile_iters is None or not args.full:
+        args.profile_iters = 20 if args.full else 0
     if args.no_extras:
         legs = {'main'}
     if args.no_cpu_baseline:
@@ -1041,7 +1096,7 @@ def main():
             else:
                 dist.init_process_group(backend)
 
-    tfile = traffic_file()
+    tfile = traffic_file() if args.full else None
     out = {} if rank == 0 else None
     wl = args.workload
     if world > 1 and not args.rehearse_shard:
@@ -1111,6 +1166,13 @@ def bench_workload(wl, args, world, rank, dist, tfile, steps, shard_of=None):
     log('%s: %d iterations in %.3f s: %.1f it/s (f %.6e, stop flag %g, iteration %g)'
         % (wl, steps, el, it_s, sc[4], sc[0], sc[1]))
     m, n_g, nz_g, p_g, nnz_g = eng.m, eng.n, eng.nz, eng.layout.p, sh['A'].nnz
+    if getattr(args, 'dump_outputs', None) and wl == args.workload and rank == 0:
+        # (before the kernel table: its stage launches run on the same buffers)
+        last = args.warmup + steps * len(els)
+        dump_outputs(args.dump_outputs,
+                     {'z': eng.current_z(last & 1), 'x': eng.x[:eng.n],
+                      'r': eng.residual_value(), 'scalars': eng.scal})
+        log('outputs of iteration %d written to %s' % (last, args.dump_outputs))
     kern = {}
     if args.profile_iters > 0 and rank == 0:
         kern = kernel_table(eng, 1 + args.warmup + steps * len(els), args.profile_iters,

@@ -135,7 +135,7 @@ def _main_rank(rank, world, port, q, fail):
 
     bench.selfcheck_sharded = fake_check
     bench.bench_workload = fake_workload
-    sys.argv = ['bench.py', '--gpus', str(world), '--steps', '2', '--warmup', '1']
+    sys.argv = ['bench.py', '--gpus', str(world), '--steps', '2', '--warmup', '1', '--full']
     buf, real = io.StringIO(), sys.stdout
     sys.stdout = buf
     code = 0
@@ -182,3 +182,77 @@ def test_main_n2_selfcheck_mismatch_exits_nonzero_untimed():
         assert code == 3 and calls == ['selfcheck'], (code, calls)
     line = json.loads(res[0][2].strip().splitlines()[-1])
     assert line['value'] is None and line['selfcheck_err'] == 1e-3 and 'error' in line
+
+
+# ---- the plain run, --full and --dump-outputs ----------------------------------
+
+def _run_n1(monkeypatch, capsys, *argv):
+    """bench.main() at N = 1 with the GPU legs replaced: (calls, line)."""
+    calls = []
+
+    def fake_workload(wl, args, world_, rank_, dist, tfile, steps, shard_of=None):
+        calls.append(('timed:' + wl, steps, args.windows, args.profile_iters, tfile is not None))
+        return {'value': 2.0, 'unit': 'it/s', 'ms_per_step': 500.0}
+
+    def fake_extras(args, legs, out, tfile):
+        calls.append(('extras', tuple(sorted(legs))))
+
+    monkeypatch.setattr(bench, 'bench_workload', fake_workload)
+    monkeypatch.setattr(bench, 'extras', fake_extras)
+    for k in ('WORLD_SIZE', 'RANK', 'LOCAL_RANK'):
+        monkeypatch.delenv(k, raising=False)
+    monkeypatch.setattr(sys, 'argv', ['bench.py'] + list(argv))
+    bench.main()
+    return calls, json.loads(capsys.readouterr().out.strip().splitlines()[-1])
+
+
+def test_plain_run_is_the_headline_alone(monkeypatch, capsys):
+    calls, line = _run_n1(monkeypatch, capsys, '--gpus', '1', '--steps', '7', '--warmup', '3')
+    # one workload, exactly --steps timed steps (one window), no kernel table,
+    # no traffic file, no further leg
+    assert calls == [('timed:C3', 7, 1, 0, False)]
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in line, key
+    assert line['metric'] == bench.METRIC and line['steps'] == 7 and line['warmup'] == 3
+    assert line['higher_is_better'] is True and line['dtype'] == 'f64'
+
+
+def test_full_run_keeps_every_leg(monkeypatch, capsys):
+    calls, line = _run_n1(monkeypatch, capsys, '--gpus', '1', '--steps', '7', '--warmup', '3',
+                          '--full')
+    assert calls[0] == ('timed:C3', 7, 10, 20, True)
+    assert calls[1][:2] == ('timed:C5', 100)
+    assert calls[2] == ('extras', tuple(sorted(bench.LEGS)))
+    assert line['c5']['value'] == 2.0
+    calls, _ = _run_n1(monkeypatch, capsys, '--full', '--legs', 'proj,iso')
+    assert calls == [('extras', ('iso', 'proj'))]
+
+
+def test_legs_beyond_the_headline_need_full(monkeypatch, capsys):
+    import pytest
+    with pytest.raises(SystemExit) as e:
+        _run_n1(monkeypatch, capsys, '--legs', 'proj')
+    assert e.value.code == 2
+
+
+def test_dump_outputs_whole_then_a_fixed_sample(tmp_path):
+    rs = np.random.RandomState(3)
+    arrays = {'z': rs.randn(5000), 'x': rs.randn(7000).astype(np.float32), 'scalars': rs.randn(16)}
+    kept = bench.dump_outputs(str(tmp_path / 'a'), arrays)
+    assert kept == {'z': 5000, 'x': 7000, 'scalars': 16}
+    for name, a in arrays.items():
+        got = np.load(tmp_path / 'a' / (name + '.npy'))
+        assert got.dtype == np.float64 and np.array_equal(got, a.astype(np.float64))
+    # over the budget: every array keeps the same share, the same entries on
+    # every call, and the files fit the budget
+    budget = 40000
+    k1 = bench.dump_outputs(str(tmp_path / 'b'), arrays, budget=budget)
+    k2 = bench.dump_outputs(str(tmp_path / 'c'), arrays, budget=budget)
+    assert k1 == k2 and 0 < k1['z'] < 5000 and 0 < k1['x'] < 7000
+    size = 0
+    for name, a in arrays.items():
+        b, c = (np.load(tmp_path / d / (name + '.npy')) for d in 'bc')
+        assert np.array_equal(b, c) and b.size == k1[name]
+        assert np.all(np.isin(b, a.astype(np.float64)))
+        size += os.path.getsize(tmp_path / 'b' / (name + '.npy'))
+    assert size <= budget

@@ -45,7 +45,7 @@ for s in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
       rc=$?; echo "smoke rc=$rc" | tee -a $OUT/status.txt; fatal $rc ;;
     bench)
-      timeout -k 10 600 python bench.py > $OUT/bench.log 2>&1
+      timeout -k 10 600 python bench.py --full > $OUT/bench.log 2>&1
       rc=$?; echo "bench rc=$rc" | tee -a $OUT/status.txt; fatal $rc ;;
     alltests)
       timeout -k 10 900 python -u -m pytest $TESTS -m gpu -q --timeout 300 --timeout-method thread \
@@ -56,13 +56,13 @@ for s in $STEPS; do
       timeout -k 10 600 python bench.py --steps 20 --warmup 5 > $OUT/bench_driverlike.log 2>&1
       rc=$?; echo "driverlike rc=$rc" | tee -a $OUT/status.txt; fatal $rc ;;
     legs)
-      timeout -k 10 600 python bench.py --legs "${LEGS:-lbfgs}" > $OUT/bench_legs.log 2>&1
+      timeout -k 10 600 python bench.py --full --legs "${LEGS:-lbfgs}" > $OUT/bench_legs.log 2>&1
       rc=$?; echo "legs rc=$rc" | tee -a $OUT/status.txt; fatal $rc ;;
     exit)
       timeout -k 10 300 python tools/exit_iters.py > $OUT/exit_iters.log 2>&1
       rc=$?; echo "exit rc=$rc" | tee -a $OUT/status.txt; fatal $rc ;;
     rehearse)
-      timeout -k 10 400 python bench.py --rehearse-shard 8 --steps 200 --warmup 20 \
+      timeout -k 10 400 python bench.py --full --rehearse-shard 8 --steps 200 --warmup 20 \
           > $OUT/rehearse8.log 2>&1
       rc=$?; echo "rehearse rc=$rc" | tee -a $OUT/status.txt; fatal $rc ;;
     pmc)
@@ -82,7 +82,7 @@ for s in $STEPS; do
         python3 tools/traffic.py $cfg $OUT/traffic_r06.json $OUT/pmc_${cfg}_1 $OUT/pmc_${cfg}_2 \
             > /dev/null 2> $OUT/traffic_$cfg.err
       done
-      # rank 0 of the 8-way C5 split (the rehearsal bench.py --rehearse-shard 8
+      # rank 0 of the 8-way C5 split (the rehearsal bench.py --full --rehearse-shard 8
       # runs): its kernels keyed C5_x8, as bench.py reads them at N > 1
       if [ -n "${PMC_X8:-1}" ]; then
         i=0
@@ -90,7 +90,7 @@ for s in $STEPS; do
           i=$((i+1))
           rm -rf $OUT/pmc_C5x8_$i
           timeout -s KILL 400 rocprofv3 --pmc $grp --output-format csv -d $OUT/pmc_C5x8_$i -o pmc \
-              -- python3 bench.py --rehearse-shard 8 --steps 30 --warmup 5 --windows 1 > $OUT/pmc_C5x8_$i.log 2>&1
+              -- python3 bench.py --full --rehearse-shard 8 --steps 30 --warmup 5 --windows 1 > $OUT/pmc_C5x8_$i.log 2>&1
           rc=$?; echo "pmc C5x8 $i rc=$rc" | tee -a $OUT/status.txt; fatal $rc
         done
         python3 tools/traffic.py C5_x8 $OUT/traffic_r06.json $OUT/pmc_C5x8_1 $OUT/pmc_C5x8_2 \
@@ -109,7 +109,7 @@ for s in $STEPS; do
             d=$OUT/pmcx_${wl}_${n}_$i
             rm -rf $d
             timeout -s KILL 300 rocprofv3 --pmc $grp --output-format csv -d $d -o pmc \
-                -- python3 bench.py --rehearse-shard $n --rehearse-workload $wl --steps 30 --warmup 5 --windows 1 \
+                -- python3 bench.py --full --rehearse-shard $n --rehearse-workload $wl --steps 30 --warmup 5 --windows 1 \
                 > $d.log 2>&1
             rc=$?; echo "pmcx $wl $n $i rc=$rc" | tee -a $OUT/status.txt; fatal $rc
           done
@@ -133,13 +133,13 @@ for s in $STEPS; do
     prof)
       for k in $PROF; do
         case "$k" in
-          C3)    prof C3 --legs main --steps 200 --warmup 10 ;;
-          C5)    prof C5 --legs c5 --steps 100 --warmup 10 ;;
-          gdlbfgs) prof gdlbfgs --legs gdlbfgs ;;
-          C2)    prof C2 --legs proj ;;
-          C4iso) prof C4iso --legs iso ;;
-          md_xs) prof md_xs --legs xspace,md,dore,lbfgs ;;
-          C5x8)  prof C5_x8 --rehearse-shard 8 --steps 100 --warmup 10 ;;
+          C3)    prof C3 --full --legs main --steps 200 --warmup 10 ;;
+          C5)    prof C5 --full --legs c5 --steps 100 --warmup 10 ;;
+          gdlbfgs) prof gdlbfgs --full --legs gdlbfgs ;;
+          C2)    prof C2 --full --legs proj ;;
+          C4iso) prof C4iso --full --legs iso ;;
+          md_xs) prof md_xs --full --legs xspace,md,dore,lbfgs ;;
+          C5x8)  prof C5_x8 --full --rehearse-shard 8 --steps 100 --warmup 10 ;;
         esac
       done ;;
   esac

@@ -14,7 +14,7 @@ for spec in "${LIST[@]}"; do
   set -- $spec
   M=""; [ "$2" != none ] && M="--model-exchange $2"
   E=""; [ "$3" = g8 ] && E="15625,8"; [ "$3" = g16 ] && E="15625,16"; [ "$3" = h2 ] && E="7813,4"; [ "$3" = h4 ] && E="3907,4"
-  BSLS_TILE_PLAN_A=$E timeout -k 10 400 python -u bench.py --rehearse-shard 8 --parts $1 $M --steps 100 --windows 5 > $OUT/reh_p$1_$2_$3.json 2> $OUT/reh_p$1_$2_$3.err || { echo "fail $spec" >> $OUT/summary.txt; cat $OUT/summary.txt; exit 1; }
+  BSLS_TILE_PLAN_A=$E timeout -k 10 400 python -u bench.py --full --rehearse-shard 8 --parts $1 $M --steps 100 --windows 5 > $OUT/reh_p$1_$2_$3.json 2> $OUT/reh_p$1_$2_$3.err || { echo "fail $spec" >> $OUT/summary.txt; cat $OUT/summary.txt; exit 1; }
   python -c "
 import json; d = json.loads(open('$OUT/reh_p$1_$2_$3.json').read().strip().splitlines()[-1])
 k = d.get('kernels', {})

@@ -10,7 +10,7 @@ BSLS_LIB=$L/libbsls_hip_w16.so timeout -k 10 300 python -u -m pytest tests/test_
 tail -2 $OUT/tests_w16.log
 for rep in 1 2 3; do
   for v in "" _w16; do
-    BSLS_LIB=$L/libbsls_hip$v.so timeout -k 10 120 python -u bench.py --legs proj > $OUT/proj$v.$rep.json 2> $OUT/proj$v.$rep.err || { echo "bench failed $v"; tail -5 $OUT/proj$v.$rep.err; exit 1; }
+    BSLS_LIB=$L/libbsls_hip$v.so timeout -k 10 120 python -u bench.py --full --legs proj > $OUT/proj$v.$rep.json 2> $OUT/proj$v.$rep.err || { echo "bench failed $v"; tail -5 $OUT/proj$v.$rep.err; exit 1; }
     python -c "
 import json; d = json.loads(open('$OUT/proj$v.$rep.json').read().strip().splitlines()[-1])
 for k in ('proj_simplex', 'proj_simplex_fast'):

@@ -11,8 +11,8 @@ BSLS_LIB=$L/libbsls_hip_ls.so timeout -k 10 900 python -u -m pytest tests/test_g
 tail -2 $OUT/tests_ls.log
 for rep in 1 2; do
   for v in "" _ls; do
-    BSLS_LIB=$L/libbsls_hip$v.so timeout -k 10 200 python -u bench.py --legs main,c5 --steps 200 --warmup 20 > $OUT/main$v.$rep.json 2> $OUT/main$v.$rep.err || { echo "bench failed $v"; tail -5 $OUT/main$v.$rep.err; exit 1; }
-    BSLS_LIB=$L/libbsls_hip$v.so timeout -k 10 200 python -u bench.py --rehearse-shard 8 --steps 100 --windows 5 > $OUT/reh$v.$rep.json 2> $OUT/reh$v.$rep.err || { echo "rehearsal failed $v"; tail -5 $OUT/reh$v.$rep.err; exit 1; }
+    BSLS_LIB=$L/libbsls_hip$v.so timeout -k 10 200 python -u bench.py --full --legs main,c5 --steps 200 --warmup 20 > $OUT/main$v.$rep.json 2> $OUT/main$v.$rep.err || { echo "bench failed $v"; tail -5 $OUT/main$v.$rep.err; exit 1; }
+    BSLS_LIB=$L/libbsls_hip$v.so timeout -k 10 200 python -u bench.py --full --rehearse-shard 8 --steps 100 --windows 5 > $OUT/reh$v.$rep.json 2> $OUT/reh$v.$rep.err || { echo "rehearsal failed $v"; tail -5 $OUT/reh$v.$rep.err; exit 1; }
     python -c "
 import json
 d = json.loads(open('$OUT/main$v.$rep.json').read().strip().splitlines()[-1])

@@ -28,11 +28,11 @@ for s in $STEPS; do
       timeout -k 10 300 python -c "import __graft_entry__ as g; g.smoke()" > $OUT/smoke.log 2>&1
       rc=$?; echo "smoke rc=$rc" | tee -a $OUT/status.txt; fatal $rc ;;
     bench)
-      timeout -k 10 600 python bench.py > $OUT/bench.log 2>&1
+      timeout -k 10 600 python bench.py --full > $OUT/bench.log 2>&1
       rc=$?; echo "bench rc=$rc" | tee -a $OUT/status.txt; fatal $rc ;;
     prof)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/prof -o run \
-          -- python3 bench.py --steps 100 --warmup 10 --no-cpu-baseline > $OUT/prof.log 2>&1
+          -- python3 bench.py --full --steps 100 --warmup 10 --no-cpu-baseline > $OUT/prof.log 2>&1
       rc=$?; echo "prof rc=$rc" | tee -a $OUT/status.txt; fatal $rc ;;
     list)
       timeout -k 10 120 rocprofv3 -L > $OUT/counters.txt 2>&1
