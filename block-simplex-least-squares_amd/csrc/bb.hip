@@ -111,6 +111,65 @@ __device__ __forceinline__ double colv_t(const bsls_bb_problem &P, int64_t i) {
     else return P.colv[i];
 }
 
+// The hand-offs between the iteration's kernels, each change behind a switch
+// of its own (A/B variant builds: make VAR=_x DEFS=-DBSLS_K1_SUM_PAIRS=0 ...;
+// the measurements: profiles/handoff_ab.txt):
+//   BSLS_K1_SUM_EARLY  bb_k1_sum issues its first rows' loads before its stop
+//                      test resolves (one memory round trip instead of two)
+//   BSLS_K1_SUM_PAIRS  bb_k1_sum takes two adjacent rows per thread with 16-B
+//                      loads and stores where m and the first row are even
+//   BSLS_WT_RPART      the split K1's partials leave through write-through
+//                      stores (as K3's z / dz / x): no dirty lines for the
+//                      kernel's end to flush before bb_k1_sum starts
+//                      (the same for K2's g and bb_k1_sum's r measured
+//                      slower and is not in the source)
+// BSLS_PHASE_STAMPS: a diagnostic build, never the product library -- wave 0
+// of every workgroup of bb_k2t, bb_k3, bb_k1t and bb_k1_sum keeps
+// s_memrealtime at its phase boundaries and leaves them in a buffer of this
+// build's own (tools/phase_times.py reads it through bsls_phase_read).
+#ifndef BSLS_K1_SUM_EARLY
+#define BSLS_K1_SUM_EARLY 1
+#endif
+#ifndef BSLS_K1_SUM_PAIRS
+#define BSLS_K1_SUM_PAIRS 1
+#endif
+#ifndef BSLS_WT_RPART
+#define BSLS_WT_RPART 1
+#endif
+
+#ifdef BSLS_PHASE_STAMPS
+constexpr int PH_SLOTS = 8, PH_WGS = 4096;
+enum { PH_K2 = 0, PH_K3 = 1, PH_K1 = 2, PH_SUM = 3 };
+__device__ unsigned long long bsls_phase_buf[4][PH_WGS][PH_SLOTS];
+#define PH_DECL unsigned long long ph_t[PH_SLOTS] = {0, 0, 0, 0, 0, 0, 0, 0}
+#define PH(s) (ph_t[s] = __builtin_amdgcn_s_memrealtime())
+#define PH_FLUSH(k)                                                            \
+    do {                                                                       \
+        if (threadIdx.x == 0 && blockIdx.x < PH_WGS)                           \
+            for (int ph_s = 0; ph_s < PH_SLOTS; ++ph_s)                        \
+                bsls_phase_buf[k][blockIdx.x][ph_s] = ph_t[ph_s];              \
+    } while (0)
+#else
+#define PH_DECL
+#define PH(s) ((void)0)
+#define PH_FLUSH(k) ((void)0)
+#endif
+
+// 8-B write-through (sc1) store through a buffer resource: the line
+// leaves L2 at once instead of as a dirty line at the kernel's end (as
+// proj.hip's store-out).  Lanes whose offset is past the resource's bytes are
+// dropped by the hardware.
+typedef double bb_d2 __attribute__((ext_vector_type(2)));
+__device__ __forceinline__ void wt_store_f64(const __amdgpu_buffer_rsrc_t &rs, int off,
+                                             double v) {
+    __builtin_amdgcn_raw_buffer_store_b64(
+        __builtin_bit_cast(HIP_vector_type<unsigned, 2>::Native_vec_, v), rs, off, 0, 16);
+}
+// the resource over `count` doubles at p (count * 8 < 2^31 by the callers)
+__device__ __forceinline__ __amdgpu_buffer_rsrc_t wt_rsrc(double *p, int64_t count) {
+    return __builtin_amdgcn_make_buffer_rsrc(p, 0, (int)(count * 8), 0x00020000);
+}
+
 // solvers.py:40-63 on iteration iter's g.g and dg.dg (the all-reduced sums)
 __device__ __forceinline__ int bb_stop_reason(const bsls_bb_problem &P, int64_t iter, double fx,
                                               double gg, double dgdg) {
@@ -285,39 +344,88 @@ __global__ __launch_bounds__(1024) void bb_k1(bsls_bb_problem P, int64_t iter, u
 // K1's finish as its own launch (rows [r0, r1), one thread per row): r = the G
 // partials in group order (+ target, ADD), ||r||^2 and f by the last block
 // (REDUCE), as k1_finish.
-template <bool ITER, bool ADD, bool REDUCE>
+// W = 2 (BSLS_K1_SUM_PAIRS; the launch: m and r0 even, r1 - r0 >= 2, 16-B
+// aligned arrays): item idx of a thread is the row pair r0 + 2 idx, + 1,
+// loaded and stored as 16 bytes; the single last row of an odd r1 - r0 is
+// the grid's last thread's, after its pairs.  W = 1: an item is a row.  A
+// thread's first item is loaded at a clamped index before the stop test
+// (BSLS_K1_SUM_EARLY: the flag's round trip and the rows' run together;
+// nothing is stored before the test).
+template <int W>
+struct K1SumVec {
+    typedef double type;
+};
+template <>
+struct K1SumVec<2> {
+    typedef bb_d2 type;
+};
+__device__ __forceinline__ double k1_sq(double o) { return o * o; }
+__device__ __forceinline__ double k1_sq(bb_d2 o) { return o.x * o.x + o.y * o.y; }
+
+template <bool ITER, bool ADD, bool REDUCE, int W = 1>
 __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter, int64_t G,
                                                  int64_t r0, int64_t r1, double *part,
                                                  unsigned *ticket) {
+    typedef typename K1SumVec<W>::type vec;
     __shared__ double red[8];
-    if (ITER && P.scal[BSLS_S_STOP] != 0.0) {
-        k1_stopped_rows(P, r0, r1, (int64_t)blockIdx.x * blockDim.x + threadIdx.x,
-                        (int64_t)gridDim.x * blockDim.x);
-        return;
-    }
-    // grid-stride rows: with REDUCE the launch is capped at K1_SUM_GRID
+    PH_DECL;
+    PH(0);
+    const double stop = ITER ? P.scal[BSLS_S_STOP] : 0.0;
+    // grid-stride items: with REDUCE the launch is capped at K1_SUM_GRID
     // workgroups (one per 256 rows made 3.9k arrivals at the ||r||^2 tickets
     // at m = 1M: 12.5 us against 4.6 without the reduction)
     const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    double sq[1] = {0.0};
-    for (int64_t row = r0 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; row < r1; row += gs) {
-        double v[8];
+    const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    int64_t idx = t0;
+    const int64_t ni = (r1 - r0) / W;   // whole items (>= 1)
+    vec v[8], tg;
+    auto load = [&](int64_t i) {
+        const int64_t row = r0 + W * (i < ni ? i : ni - 1);
 #pragma unroll
-        for (int c = 0; c < 8; ++c) v[c] = (c < G) ? P.rpart[c * P.m + row] : 0.0;
-        double o = v[0];
+        for (int c = 0; c < 8; ++c)
+            v[c] = (c < G) ? *reinterpret_cast<const vec *>(&P.rpart[c * P.m + row]) : vec{};
+        tg = ADD ? *reinterpret_cast<const vec *>(&P.target[row]) : vec{};
+    };
+    if (BSLS_K1_SUM_EARLY) load(idx);
+    if (ITER && stop != 0.0) {
+        k1_stopped_rows(P, r0, r1, t0, gs);
+        return;
+    }
+    PH(1);
+    if (!BSLS_K1_SUM_EARLY) load(idx);
+    double sq[1] = {0.0};
+    while (idx < ni) {
+        const int64_t row = r0 + W * idx;
+        vec o = v[0];
 #pragma unroll
         for (int c = 1; c < 8; ++c)
             if (c < G) o += v[c];
-        for (int64_t c = 8; c < G; ++c) o += P.rpart[c * P.m + row];
+        for (int64_t c = 8; c < G; ++c) o += *reinterpret_cast<const vec *>(&P.rpart[c * P.m + row]);
+        if (ADD) o += tg;
+        *reinterpret_cast<vec *>(&P.r[row]) = o;
+        sq[0] += k1_sq(o);
+        idx += gs;
+        if (idx < ni) load(idx);
+    }
+    if (W == 2 && ((r1 - r0) & 1) && t0 == gs - 1) {
+        const int64_t row = r1 - 1;
+        double o = P.rpart[row];
+        for (int64_t c = 1; c < G; ++c) o += P.rpart[c * P.m + row];
         if (ADD) o += P.target[row];
         P.r[row] = o;
         sq[0] += o * o;
     }
-    if (!REDUCE) return;
+    PH(2);
+    if (!REDUCE) {
+        PH_FLUSH(PH_SUM);
+        return;
+    }
     block_sum<1>(sq, red);
     double tot[1];
     if (last_block_sum<1>(sq, part, ticket, tot, red) && threadIdx.x == 0)
         bb_record_f(P, iter, tot[0], ITER);
+    PH(3);
+    PH_FLUSH(PH_SUM);
 }
 
 // K1 with global atomics (BSLS_K1_ATOMIC): rows [r0, r1) of r start as
@@ -353,6 +461,8 @@ __global__ __launch_bounds__(1024, BSLS_K1T_WGS) void bb_k1t(bsls_bb_problem P, 
     __shared__ double red[32];   // (k1_finish: 2 doubles per wave)
     __shared__ int row_last;
     const bsls_tiles &T = P.At;
+    PH_DECL;
+    PH(0);
     int64_t rb, g;
     tile_map(T, blockIdx.x, gridDim.x / T.ngroups, rb, g);
     rb += rb_base;
@@ -365,15 +475,26 @@ __global__ __launch_bounds__(1024, BSLS_K1T_WGS) void bb_k1t(bsls_bb_problem P, 
         return;
     }
     const int HR = (int)tile_lds_doubles(T, false);
-    for (int i = threadIdx.x; i < HR; i += blockDim.x) lds[i] = 0.0;
+    // (the clear and its barrier: under the dealt walk's first loads, tiles.hpp
+    // BSLS_WALK_PREFILL)
+    PH(1);
+    auto clear = [&]() {
+        PH(2);
+        for (int i = threadIdx.x; i < HR; i += blockDim.x) lds[i] = 0.0;
+        __syncthreads();
+        PH(3);
+    };
+    tile_walk_any<MODE>(T, rb, g, P.x, lds, nullptr, 1.0, 1.0, clear);
+    PH(4);
     __syncthreads();
-    tile_walk_any<MODE>(T, rb, g, P.x, lds, nullptr);
-    __syncthreads();
+    PH(5);
     const int64_t G = T.ngroups;
     const int64_t r0 = rb * T.H, r1 = (r0 + T.H < P.m) ? r0 + T.H : P.m;
     if (G == 1) {
         k1_finish<ADD, REDUCE>(P, iter, ITER, rb, (unsigned)T.nrb, r0, r1, 1, lds, part, ticket,
                                red);
+        PH(6);
+        PH_FLUSH(PH_K1);
         return;
     }
     if (ATOM) {
@@ -393,8 +514,19 @@ __global__ __launch_bounds__(1024, BSLS_K1T_WGS) void bb_k1t(bsls_bb_problem P, 
     }
     if (BSLS_K1_SPLIT) {
         // the partials only; bb_k1_sum (next in the stream) finishes the rows
+        if (BSLS_WT_RPART) {
+            // (a row block's sums fit LDS: the offsets stay far below 2^31)
+            const __amdgpu_buffer_rsrc_t rp = wt_rsrc(P.rpart + g * P.m + r0, r1 - r0);
+            for (int64_t row = r0 + threadIdx.x; row < r1; row += blockDim.x)
+                wt_store_f64(rp, (int)(row - r0) * 8, lds[row - r0]);
+            PH(6);
+            PH_FLUSH(PH_K1);
+            return;
+        }
         for (int64_t row = r0 + threadIdx.x; row < r1; row += blockDim.x)
             P.rpart[g * P.m + row] = lds[row - r0];
+        PH(6);
+        PH_FLUSH(PH_K1);
         return;
     }
     for (int64_t row = r0 + threadIdx.x; row < r1; row += blockDim.x)
@@ -474,10 +606,13 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double red[5 * 16];
     __shared__ int row_last;
+    PH_DECL;
+    PH(0);
     if (ITER && P.scal[BSLS_S_STOP] != 0.0) {
         if (gsel < 0 || gsel == P.ATt.ngroups - 1) k2_stopped_sums<FUSE>(P);
         return;
     }
+    PH(1);
     const bsls_tiles &T = P.ATt;
     int64_t rb, g;
     if (gsel >= 0) {
@@ -523,17 +658,25 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
             }
         }
     }
-    for (int i = threadIdx.x; i < HR; i += blockDim.x) {
-        rows[i] = 0.0;
-        if (MODE == 2) rc[i] = (i < nloc) ? colv_t<CV>(P, i0 + i) : 0.0;
-    }
-    __syncthreads();
+    // (the clear and its barrier: under the dealt walk's first loads, tiles.hpp
+    // BSLS_WALK_PREFILL)
+    auto clear = [&]() {
+        PH(2);
+        for (int i = threadIdx.x; i < HR; i += blockDim.x) {
+            rows[i] = 0.0;
+            if (MODE == 2) rc[i] = (i < nloc) ? colv_t<CV>(P, i0 + i) : 0.0;
+        }
+        __syncthreads();
+        PH(3);
+    };
     if (P.r_fx > 0.0)
         tile_walk_any<(MODE == 3 ? 0 : MODE), false, true>(T, rb, g, P.r, rows, rc, 1.0,
-                                                            1.0 / P.r_fx);
+                                                            1.0 / P.r_fx, clear);
     else
-        tile_walk_any<(MODE == 3 ? 0 : MODE)>(T, rb, g, P.r, rows, rc);
+        tile_walk_any<(MODE == 3 ? 0 : MODE)>(T, rb, g, P.r, rows, rc, 1.0, 1.0, clear);
+    PH(4);
     __syncthreads();
+    PH(5);
     // wpart's tail: one slot per (group, row block) for the slices' r^2 sums
     double *rrp = P.wpart + G * T.nrb * (T.H + 1);
     if (FUSE && ITER && G > 1) {
@@ -642,7 +785,11 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
             }
         }
     }
-    if (!ITER || !fin) return;
+    PH(6);
+    if (!ITER || !fin) {
+        PH_FLUSH(PH_K2);
+        return;
+    }
     if constexpr (FUSE) {
         if (G == 1) {
             sums[4] = rr[0];
@@ -686,6 +833,8 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
         P.scal[BSLS_S_DGDG] = tot[2];
         P.scal[BSLS_S_GG] = tot[3];
     }
+    PH(7);
+    PH_FLUSH(PH_K2);
 }
 
 // Stage 12 (the sliced schedule, after the all-reduce of scal[SUMDG..RR]):
@@ -895,15 +1044,6 @@ __device__ __forceinline__ bool bb_step_t(const bsls_bb_problem &P, int64_t iter
     return true;
 }
 
-// 8-B write-through (sc1) store through a buffer resource: the line leaves L2
-// at once instead of as a dirty line at the kernel's end (as proj.hip's
-// store-out).  Lanes whose offset is past `bytes` are dropped by the hardware.
-__device__ __forceinline__ void wt_store_f64(const __amdgpu_buffer_rsrc_t &rs, int off,
-                                             double v) {
-    __builtin_amdgcn_raw_buffer_store_b64(
-        __builtin_bit_cast(HIP_vector_type<unsigned, 2>::Native_vec_, v), rs, off, 0, 16);
-}
-
 #ifndef BSLS_K3_SGPRS
 #define BSLS_K3_SGPRS 80
 #endif
@@ -926,6 +1066,8 @@ void bb_k3(bsls_bb_problem P, int64_t iter,
                                              double *__restrict__ dzo,
                                              int32_t *__restrict__ wsc, int rec,
                                              uint64_t *__restrict__ hd, int kinit) {
+    PH_DECL;
+    PH(0);
     const double sc[4] = {P.scal[BSLS_S_STOP], P.scal[BSLS_S_SUMDG], P.scal[BSLS_S_DZDG],
                           P.scal[BSLS_S_DGDG]};
     // kinit (stage 15): the next K1's r initialisation folded in (its atomic
@@ -1012,10 +1154,16 @@ void bb_k3(bsls_bb_problem P, int64_t iter,
     const bool go = bb_step_t(P, iter, sc, t);
     if (kinit) init_r(!go);
     if (!go) return;
+    PH(1);
     double yv[K3_PPW];
 #pragma unroll
     for (int q = 0; q < K3_PPW; ++q)   // x_next = x - t g (BB.py:29)
         yv[q] = (l < L[q] && L[q] <= WAVE) ? zv[q] - t * gv[q] : 0.0;
+#ifdef BSLS_PHASE_STAMPS
+    // (the stamp after z and g have landed: it waits for them through yv)
+    asm volatile("" ::"v"(yv[0]));
+    PH(2);
+#endif
     if (BSLS_K3_KO != 1) {
         // warm start: the last run partition of each pack, tested first
         // (pava_warm); a pack that passes needs no reference pass
@@ -1053,6 +1201,7 @@ void bb_k3(bsls_bb_problem P, int64_t iter,
                 if (store[q] && l == 0) hd[w0 + q * nw] = Hn[q];
         }
     }
+    PH(3);
 #pragma unroll
     for (int q = 0; q < K3_PPW; ++q) {
         if (L[q] == 0) break;
@@ -1103,6 +1252,8 @@ void bb_k3(bsls_bb_problem P, int64_t iter,
             x_put(P, xo, 0.0 - prev);
         }
     }
+    PH(4);
+    PH_FLUSH(PH_K3);
 }
 
 // K3 for one z-block longer than a wave, one 1024-thread workgroup per block
@@ -1247,6 +1398,15 @@ static void launch_k1t_mode(const bsls_bb_problem &P, int64_t iter, const BBWork
     if (BSLS_K1_SPLIT && P.At.ngroups > 1) {
         const int64_t r0 = rb0 * P.At.H, r1 = (rb1 * P.At.H < P.m) ? rb1 * P.At.H : P.m;
         constexpr int K1_SUM_GRID = 1024;
+        // rows in 16-B pairs where every pair is aligned in rpart, target and r
+        const bool pairs = BSLS_K1_SUM_PAIRS && !(P.m & 1) && !(r0 & 1) && r1 - r0 >= 2 &&
+                           !(((uintptr_t)P.rpart | (uintptr_t)P.target | (uintptr_t)P.r) & 15);
+        if (pairs) {
+            const int gk = grid_for((r1 - r0) / 2, 256);
+            bb_k1_sum<ITER, ADD, REDUCE, 2><<<(REDUCE && gk > K1_SUM_GRID) ? K1_SUM_GRID : gk, 256,
+                                              0, st>>>(P, iter, P.At.ngroups, r0, r1, w.pf, w.tkf);
+            return;
+        }
         const int gk = grid_for(r1 - r0, 256);
         bb_k1_sum<ITER, ADD, REDUCE><<<(REDUCE && gk > K1_SUM_GRID) ? K1_SUM_GRID : gk, 256, 0, st>>>(
             P, iter, P.At.ngroups, r0, r1, w.pf, w.tkf);
@@ -1799,6 +1959,21 @@ extern "C" int bsls_lbfgs_ls_finish(const bsls_bb_problem *p, const bsls_ls_stat
     BSLS_LAUNCH_CHECK();
     return BSLS_OK;
 }
+
+#ifdef BSLS_PHASE_STAMPS
+// the stamps of the last launches: [kernel][workgroup][slot] -> host (after a sync)
+extern "C" int bsls_phase_read(unsigned long long *host, size_t count) {
+    const size_t all = sizeof(bsls_phase_buf) / sizeof(unsigned long long);
+    BSLS_CHECK(hipMemcpyFromSymbol(host, HIP_SYMBOL(bsls_phase_buf),
+                                   (count < all ? count : all) * sizeof(unsigned long long)));
+    return BSLS_OK;
+}
+extern "C" void bsls_phase_shape(int *shape) {
+    shape[0] = 4;
+    shape[1] = PH_WGS;
+    shape[2] = PH_SLOTS;
+}
+#endif
 
 extern "C" size_t bsls_ticket_bytes(void) { return (size_t)TICKET_BYTES; }
 

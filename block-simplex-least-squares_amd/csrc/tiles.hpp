@@ -163,6 +163,21 @@ __device__ __forceinline__ uint32_t tri_entry(const tile_tri &t, int j) {
 #ifndef BSLS_TILE_D
 #define BSLS_TILE_D 1
 #endif
+// BSLS_WALK_PREFILL: the dealt walk issues its first loads (wave_off /
+// group_col, then the P ring steps of entries and bases) BEFORE the caller's
+// `mid` step -- the clear of the LDS row sums and its barrier -- so the clear
+// runs under those loads instead of in front of them; the gathers and the LDS
+// adds start after it.  The same adds into the same zeroed rows.  A tile with
+// fewer than P steps (or none) loads only the steps it has, as before.  The
+// thread-stream walk (layout 0) runs `mid` first.  0: `mid` first everywhere
+// (A/B variant).
+#ifndef BSLS_WALK_PREFILL
+#define BSLS_WALK_PREFILL 1
+#endif
+struct TileNoMid {
+    __device__ __forceinline__ void operator()() const {}
+};
+
 template <bool PK3>
 struct TileEnt {
     typedef tile_quad type;
@@ -254,12 +269,13 @@ __device__ __forceinline__ double fx_value(const double *rows, int lr, int lo_of
 // bsls_bb_problem.r_fx): each gathered word is an int64, its value that times
 // fxin (the inverse scale)
 template <int MODE, bool NT, bool PK3 = false, int VT = 0, int P = BSLS_TILE_P,
-          int D = BSLS_TILE_D, bool FX = false, bool FXIN = false>
+          int D = BSLS_TILE_D, bool FX = false, bool FXIN = false, typename MID = TileNoMid>
 __device__ __forceinline__ void tile_walk_dealt(const bsls_tiles &T, int64_t rb, int64_t g,
                                                 const double *__restrict__ src, double *rows,
                                                 const double *rcol, double fxs = 1.0,
-                                                double fxin = 1.0) {
+                                                double fxin = 1.0, MID mid = MID()) {
     static_assert(D >= 1 && D < P, "gathers run ahead of the entry loads");
+    if (BSLS_TILE_KO == 3 || !BSLS_WALK_PREFILL) mid();
     if (BSLS_TILE_KO == 3) return;
     typedef typename TileEnt<PK3>::type ent_t;
     const int lane = threadIdx.x & 63;
@@ -293,6 +309,7 @@ __device__ __forceinline__ void tile_walk_dealt(const bsls_tiles &T, int64_t rb,
         ring[k] = (k < nq) ? ld(k) : ent_t{};
         bring[k] = (k < nq) ? Bq[(int64_t)k * 16] : int4{0, 0, 0, 0};
     }
+    if (BSLS_WALK_PREFILL) mid();   // (the caller's LDS clear and barrier, under the loads above)
     // v[d] / a[d]: the gathered values (and stored values) of step s + d
     double v[D + 1][4], a[D + 1][4];
     double ko = 0.0;
@@ -352,40 +369,48 @@ __device__ __forceinline__ void tile_walk_dealt(const bsls_tiles &T, int64_t rb,
 }
 
 // the dealt walk with its value type (MODE 1 only: the other modes store none)
-template <int MODE, bool NT, bool PK3, bool FX = false, bool FXIN = false>
+template <int MODE, bool NT, bool PK3, bool FX = false, bool FXIN = false,
+          typename MID = TileNoMid>
 __device__ __forceinline__ void tile_walk_dealt_vt(const bsls_tiles &T, int64_t rb, int64_t g,
                                                    const double *__restrict__ src, double *rows,
                                                    const double *rcol, double fxs = 1.0,
-                                                   double fxin = 1.0) {
+                                                   double fxin = 1.0, MID mid = MID()) {
     constexpr int P = BSLS_TILE_P, D = BSLS_TILE_D;
     if constexpr (MODE == 1) {
         if (T.layout & BSLS_TILE_VAL16)
-            tile_walk_dealt<MODE, NT, PK3, 2, P, D, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin);
+            tile_walk_dealt<MODE, NT, PK3, 2, P, D, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin,
+                                                              mid);
         else if (T.layout & BSLS_TILE_VAL32)
-            tile_walk_dealt<MODE, NT, PK3, 1, P, D, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin);
+            tile_walk_dealt<MODE, NT, PK3, 1, P, D, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin,
+                                                              mid);
         else
-            tile_walk_dealt<MODE, NT, PK3, 0, P, D, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin);
+            tile_walk_dealt<MODE, NT, PK3, 0, P, D, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin,
+                                                              mid);
     } else {
-        tile_walk_dealt<MODE, NT, PK3, 0, P, D, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin);
+        tile_walk_dealt<MODE, NT, PK3, 0, P, D, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin,
+                                                          mid);
     }
 }
 
 // the walk of either layout (FX, FXIN: dealt layouts only)
-template <int MODE, bool FX = false, bool FXIN = false>
+template <int MODE, bool FX = false, bool FXIN = false, typename MID = TileNoMid>
 __device__ __forceinline__ void tile_walk_any(const bsls_tiles &T, int64_t rb, int64_t g,
                                               const double *__restrict__ src, double *rows,
                                               const double *rcol, double fxs = 1.0,
-                                              double fxin = 1.0) {
+                                              double fxin = 1.0, MID mid = MID()) {
     const int64_t lay = T.layout & ~(int64_t)(BSLS_TILE_VAL32 | BSLS_TILE_VAL16);
     if (lay == 1)
-        tile_walk_dealt_vt<MODE, false, false, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin);
+        tile_walk_dealt_vt<MODE, false, false, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin, mid);
     else if (lay == (1 | BSLS_TILE_NT))
-        tile_walk_dealt_vt<MODE, true, false, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin);
+        tile_walk_dealt_vt<MODE, true, false, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin, mid);
     else if (lay == 2)
-        tile_walk_dealt_vt<MODE, false, true, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin);
+        tile_walk_dealt_vt<MODE, false, true, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin, mid);
     else if (lay == (2 | BSLS_TILE_NT))
-        tile_walk_dealt_vt<MODE, true, true, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin);
-    else if constexpr (!FX && !FXIN) tile_walk<MODE>(T, rb, g, src, rows, rcol);
+        tile_walk_dealt_vt<MODE, true, true, FX, FXIN>(T, rb, g, src, rows, rcol, fxs, fxin, mid);
+    else {
+        mid();
+        if constexpr (!FX && !FXIN) tile_walk<MODE>(T, rb, g, src, rows, rcol);
+    }
 }
 
 // Host-side validation of a tile image against the matrix it claims to hold
