@@ -155,13 +155,22 @@ __global__ __launch_bounds__(256) void line_search_kernel(const double *x, doubl
     if (threadIdx.x == 0) *f_out = sh[2];
 }
 
+// max over the wave, NaN-propagating (the reference's inf-norm is NaN then)
+__device__ __forceinline__ double wave_nan_max(double v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, WAVE));
+    return v;
+}
+
 // Mirror-descent step (mirror_descent.py:37-47): per coordinate
 // up = g * t, t = sqrt(2 ln k_b) / scale (scale = sqrt(k) Lf from the host),
 // x <- x * exp(-up), then each block divided by its sum; per-block
 // max|x_new - x_old| into part[], reduced by the last workgroup into *dxinf.
 // With `state` (gated form): nothing happens once state[0] != 0; the launch
 // that sees ||x_new - x_old||_inf < tol sets state[0] = 1 and state[2] = iter
-// (the reference's break), state[1] = the norm every launch.
+// (the reference's break), state[1] = the norm every launch.  Every max is
+// NaN-propagating, as the pack form's: a NaN in g makes the norm NaN, which is
+// never < tol (np.linalg.norm(x - x_prev, inf) at mirror_descent.py:50).
 __global__ __launch_bounds__(256) void md_kernel(double *__restrict__ x,
                                                  const double *__restrict__ g,
                                                  const int64_t *__restrict__ starts,
@@ -193,13 +202,13 @@ __global__ __launch_bounds__(256) void md_kernel(double *__restrict__ x,
         }
     }
     // block max (order-independent), then last-workgroup max over partials
-    dmax = wave_max(dmax);
+    dmax = wave_nan_max(dmax);
     if (lane_id() == 0) red[threadIdx.x / WAVE] = dmax;
     __syncthreads();
     double mine[1] = {0.0};
     if (threadIdx.x == 0) {
         double m = red[0];
-        for (int w = 1; w < (int)(blockDim.x / WAVE); ++w) m = red[w] > m ? red[w] : m;
+        for (int w = 1; w < (int)(blockDim.x / WAVE); ++w) m = nan_max(m, red[w]);
         mine[0] = m;
     }
     __shared__ int am_last;
@@ -215,7 +224,7 @@ __global__ __launch_bounds__(256) void md_kernel(double *__restrict__ x,
         double m = 0.0;
         for (unsigned i = 0; i < gridDim.x; ++i) {
             const double v = __hip_atomic_load(&part[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            m = v > m ? v : m;
+            m = nan_max(m, v);
         }
         if (dxinf) *dxinf = m;
         if (state) {
@@ -237,12 +246,6 @@ __global__ __launch_bounds__(256) void md_kernel(double *__restrict__ x,
 // entries is a pack of its own, summed by the whole wave.  Gated form only.
 __device__ __forceinline__ double md_shfl(double v, int src) { return __shfl(v, src, WAVE); }
 constexpr int MD_PACK_WAVES = 16;   // packs per 1024-thread workgroup
-// max over the wave, NaN-propagating (the reference's inf-norm is NaN then)
-__device__ __forceinline__ double wave_nan_max(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = nan_max(v, __shfl_xor(v, o, WAVE));
-    return v;
-}
 
 __global__ __launch_bounds__(1024) void md_pack_kernel(double *__restrict__ x,
                                                       const double *__restrict__ g,

@@ -124,7 +124,7 @@ def least_squares(A, b, blocks, iters=1000, tolerance=1e-9, return_iters=False, 
                   panels=None):
     """x after at most `iters` steps, stopping at the first whose
     ||x - x_prev||_inf < tolerance (mirror_descent.py:37-51).  The stopping test
-    runs on the device (bsls_md_update_gated) and the host reads it every
+    runs on the device (bsls_md_update_packs) and the host reads it every
     `poll` iterations -- iterations enqueued past the stop leave x unchanged."""
     md = MirrorDescent(A, b, blocks, panels=panels)
     md.start()

@@ -764,7 +764,9 @@ int bsls_xbb_rounds(const bsls_xbb_problem *p, int64_t count, void *stream);
  * Replaces mirror_descent.least_squares's step (python/mirror_descent.py:37-47):
  * x <- x * exp(-t_k g) per coordinate, t_k = sqrt(2 ln k_b)/(sqrt(k) Lf), then
  * every block divided by its sum; *d_dxinf receives ||x_new - x_old||_inf.
- * d_g = A'(Ax - b) computed with bsls_csr_spmv.  In place on d_x. */
+ * d_g = A'(Ax - b) computed with bsls_csr_spmv.  In place on d_x.  A NaN in a
+ * block's d_g makes that block NaN and *d_dxinf NaN (the max propagates NaN,
+ * as np.linalg.norm(., inf) does). */
 int bsls_md_update(double *d_x, const double *d_g, const int64_t *d_starts, int64_t nblocks,
                    int64_t n, double step_scale, double *d_dxinf, void *d_work,
                    size_t work_bytes, void *stream);
@@ -775,7 +777,8 @@ size_t bsls_md_workspace_size(int64_t nblocks);
  * (mirror_descent.py:50-51): d_state[3] = {stopped, last norm, stop
  * iteration}, zeroed by the caller before iteration 1; once the norm of
  * iteration `iter` is < tol, state = {1, norm, iter} and later calls leave x
- * unchanged. */
+ * unchanged.  A NaN norm (a NaN in d_g) is stored in d_state[1] and never
+ * stops the run: NaN < tol is false, as in the reference. */
 int bsls_md_update_gated(double *d_x, const double *d_g, const int64_t *d_starts, int64_t nblocks,
                          int64_t n, double step_scale, double tol, int64_t iter, double *d_state,
                          void *d_work, size_t work_bytes, void *stream);

@@ -407,3 +407,45 @@ def test_iso_plan_cache_by_content(monkeypatch):
     assert p5 is not p1 and len(made) == 5
     monkeypatch.setattr(device, '_cur_dev', lambda: -1)
     assert device.iso_plan(np.array([0, 3, 7, 12]), 20) is p1
+
+
+def test_md_pack_blocks():
+    """mirror_descent.pack_blocks (host only), the plan bsls_md_update_packs
+    walks: packs tile [0, n) in order, each a run of whole blocks with <= 64
+    entries (mask bit i = a block starts at entry i of the pack, bit 0 always)
+    or one longer block alone with mask 1, greedy; 64 singletons after a full
+    pack give the mask of all ones (int64 -1), and 63 + 1 sets bit 63."""
+    from mirror_descent import pack_blocks
+    rs = np.random.RandomState(3)
+    sizes = rs.randint(1, 50, size=3000)
+    sizes[[5, 700, 2999]] = [65, 400, 64]
+    at = 1200
+    sizes = np.concatenate((sizes[:at], [65, 63, 1], np.ones(64, dtype=np.int64), [65],
+                            sizes[at:])).astype(np.int64)
+    starts = np.concatenate(([0], np.cumsum(sizes)[:-1]))
+    n = int(sizes.sum())
+    x0, mask, ln = pack_blocks(sizes)
+    assert x0.dtype == np.int64 and mask.dtype == np.int64 and ln.dtype == np.int32
+    assert x0[0] == 0
+    ends = x0 + ln
+    assert np.array_equal(x0[1:], ends[:-1]) and ends[-1] == n
+    blk = 0
+    for q in range(x0.shape[0]):
+        m, L = int(mask[q]) & 0xFFFFFFFFFFFFFFFF, int(ln[q])
+        nb = bin(m).count('1')
+        assert m & 1
+        assert np.array_equal(starts[blk:blk + nb] - x0[q], [i for i in range(64) if (m >> i) & 1])
+        assert int(sizes[blk:blk + nb].sum()) == L
+        if L > 64:
+            assert nb == 1 and m == 1
+        else:
+            # greedy: the next block would not have fitted
+            nxt = sizes[blk + nb] if blk + nb < sizes.size else 0
+            assert blk + nb == sizes.size or L + nxt > 64
+        blk += nb
+    assert blk == sizes.size
+    q = int(np.searchsorted(x0, starts[at + 1]))          # the pack of the 63 + 1
+    assert x0[q] == starts[at + 1] and ln[q] == 64
+    assert int(mask[q]) & 0xFFFFFFFFFFFFFFFF == 1 | (1 << 63)
+    assert ln[q + 1] == 64 and mask[q + 1] == -1          # the 64 singletons
+    assert ln[q + 2] == 65 and mask[q + 2] == 1
