@@ -85,7 +85,8 @@ class BBProblem(ctypes.Structure):
                 ('long_packs', _vp), ('nlong', _i64), ('long_off', _vp), ('long_scratch', _vp),
                 ('colv_n', _vp), ('colv_codec', _i64), ('rr_lo', _i64), ('rr_hi', _i64),
                 ('pava_warm', _i64), ('k1_atomic', _i64), ('k3_merge', _i64), ('r_fx', _dbl),
-                ('sy_dr', _i64)]
+                ('sy_dr', _i64), ('fx_sums', _i64), ('fx_a1', _dbl), ('fx_a2', _dbl),
+                ('x_bound', _dbl)]
 
 
 class DoreState(ctypes.Structure):
@@ -182,6 +183,8 @@ _SIGS = {
                              _sz, _vp]),
     'bsls_bb_workspace_size': (_sz, [_i64, _i64, _i64]),
     'bsls_bb_dz_offset': (_sz, [_i64, _i64, _i64]),
+    'bsls_bb_rmax_offset': (_sz, [_i64, _i64, _i64]),
+    'bsls_bb_rmax_slots': (_int, []),
     'bsls_bb_long_scratch_size': (_sz, [_i64]),
     'bsls_bb_prologue': (_int, [ctypes.POINTER(BBProblem), _vp]),
     'bsls_bb_iterate': (_int, [ctypes.POINTER(BBProblem), _i64, _i64, _vp]),

@@ -34,7 +34,8 @@
 // The SpMV row sums are fixed-order on the panels and the thread-stream tiles
 // (BBEngine(deterministic=True): runs bit-reproducible); the dealt tiles, the
 // default, add them with LDS atomics, so their rounding varies run to run at
-// the 1e-16 level.
+// the 1e-16 level -- unless bsls_bb_problem.fx_sums (BBEngine(fixed_sums=True))
+// has them summed as integers in fixed point, which is order-free.
 // Scalars live in device memory (scal[]); the host only polls them.
 #include "pava.hpp"
 #include "pava_long.hpp"
@@ -53,10 +54,20 @@ struct BBWork {
     uint64_t *hd; // K3's warm start: each pack's last run-head mask (<= n - nz packs),
                   //   two sets (slot 1: DORE's second projection, the line search's trials)
     int64_t hd_stride;
+    unsigned long long *rmax;   // fx_sums: max|r| as bit patterns, RMAX_SLOTS words
     size_t bytes;
 };
 
 static size_t al16(size_t v) { return (v + 15) & ~(size_t)15; }
+
+// fx_sums (bsls_bb_problem): max|r| for K2's fixed-point scale, kept on the
+// device.  The bit patterns of non-negative doubles order as unsigned integers
+// (a NaN's above inf's), so every workgroup that finishes rows of r folds its
+// max into one of RMAX_SLOTS words with a 64-bit atomic max -- order-free,
+// hence the same bits at the same r (as lsq.hip's lsq_xmax_kernel; an atomic
+// per wave into 16 words took bb_k1_sum from 5.7 to 9.3 us at C3).  K2 reads
+// the max over the slots; K3, between K2 and the next K1 finish, clears them.
+constexpr int RMAX_SLOTS = 64;
 
 
 static BBWork bb_layout(void *base, int64_t m, int64_t n, int64_t nz) {
@@ -87,6 +98,8 @@ static BBWork bb_layout(void *base, int64_t m, int64_t n, int64_t nz) {
     w.hd = (uint64_t *)(p + off);
     w.hd_stride = n - nz > 0 ? n - nz : 1;
     off += al16((size_t)w.hd_stride * 2 * 8);
+    w.rmax = (unsigned long long *)(p + off);
+    off += al16((size_t)RMAX_SLOTS * 8);
     w.bytes = off;
     return w;
 }
@@ -212,6 +225,56 @@ __device__ __forceinline__ double r_load(const bsls_bb_problem &P, int64_t i) {
     return P.r[i];
 }
 
+__device__ __forceinline__ unsigned long long abs_bits(double v) {
+    return (unsigned long long)__double_as_longlong(fabs(v));
+}
+__device__ __forceinline__ unsigned long long umax64(unsigned long long a, unsigned long long b) {
+    return a > b ? a : b;
+}
+// a thread's max (bit pattern) -> its wave's -> its workgroup's -> one slot
+// (every thread of the workgroup calls it: one barrier)
+__device__ __forceinline__ void rmax_fold(unsigned long long *slots, unsigned long long mb) {
+    __shared__ unsigned long long wmax[16];
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) mb = umax64(mb, __shfl_xor(mb, o, WAVE));
+    if (lane_id() == 0) wmax[threadIdx.x / WAVE] = mb;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int k = 1; k < (int)(blockDim.x / WAVE); ++k) mb = umax64(mb, wmax[k]);
+        if (mb) atomicMax(slots + blockIdx.x % RMAX_SLOTS, mb);
+    }
+}
+__device__ __forceinline__ double rmax_of(const unsigned long long *slots) {
+    unsigned long long b = 0ull;
+#pragma unroll
+    for (int k = 0; k < RMAX_SLOTS; ++k) b = umax64(b, slots[k]);
+    return __longlong_as_double((long long)b);
+}
+
+// The fixed-point scale of a walk whose rows' sum |terms| stays within B:
+// B < 2^e (frexp), fxs = 2^(50 - e) puts every row within +-2^50, inv undoes
+// it.  e is kept >= -900 so the scale stays finite (a larger bound is still a
+// bound).  Returns whether B is no finite bound (a NaN or inf in what it was
+// made from): the rows are then NaN, as float sums would make them.
+__device__ __forceinline__ bool fx_scale(double B, double &fxs, double &inv) {
+    int ex = 0;
+    if (B > 0.0 && B <= 1.7976931348623157e308) (void)frexp(B, &ex);
+    if (ex < -900) ex = -900;
+    fxs = ldexp(1.0, 50 - ex);
+    inv = ldexp(1.0, ex - 50);
+    return !(B <= 1.7976931348623157e308);
+}
+// row lr's two words back to a double (tiles.hpp fx_value).  Terms within
+// the bound keep the high word inside +-2^51; one outside it holds a term
+// beyond the bound, a NaN or an inf (their bit patterns add as huge integers):
+// NaN, which the solvers' checks then see.
+__device__ __forceinline__ double fx_row(const double *rows, int lr, int lo_off, double inv,
+                                         double inv_lo, bool bad) {
+    const long long hi = reinterpret_cast<const long long *>(rows)[lr];
+    if (bad || hi > (1LL << 51) || hi < -(1LL << 51)) return __builtin_nan("");
+    return fx_value(rows, lr, lo_off, inv, inv_lo);
+}
+
 // A column-sharded rank other than the one adding target (shard_role 2)
 // writes r = 0 for its rows once the run has stopped: its K1 no longer forms a
 // partial, and the all-reduce must leave the final residual (held by the
@@ -226,18 +289,22 @@ __device__ __forceinline__ void k1_stopped_rows(const bsls_bb_problem &P, int64_
 // the G partials of each row summed in group order (from rpart, or from LDS
 // `local` when the block had one group) + target; its share of ||r||^2 goes
 // to the last row block, which records f and runs the stopping test.
-template <bool ADD, bool REDUCE>
+// FX (fx_sums): |r| of the rows folded into rmax for the next K2's scale.
+template <bool ADD, bool REDUCE, bool FX = false>
 __device__ __forceinline__ void k1_finish(const bsls_bb_problem &P, int64_t iter, bool iterating,
                                           int64_t rb, unsigned nrb, int64_t r0, int64_t r1,
                                           int64_t G, const double *local, double *part,
-                                          unsigned *ticket, double *red) {
+                                          unsigned *ticket, double *red,
+                                          unsigned long long *rmax = nullptr) {
     double sq[1] = {0.0};
+    unsigned long long mb = 0ull;
     if (local) {
         for (int64_t row = r0 + threadIdx.x; row < r1; row += blockDim.x) {
             double o = local[row - r0];
             if (ADD) o += P.target[row];
             P.r[row] = o;
             sq[0] += o * o;
+            if constexpr (FX) mb = umax64(mb, abs_bits(o));
         }
     } else {
         // up to RPT rows per thread, every partial load of them in flight at once
@@ -268,9 +335,11 @@ __device__ __forceinline__ void k1_finish(const bsls_bb_problem &P, int64_t iter
                 if (ADD) o += P.target[row];
                 P.r[row] = o;
                 sq[0] += o * o;
+                if constexpr (FX) mb = umax64(mb, abs_bits(o));
             }
         }
     }
+    if constexpr (FX) rmax_fold(rmax, mb);
     if (!REDUCE) return;
     block_sum<1>(sq, red);
     double tot[1];
@@ -361,11 +430,17 @@ struct K1SumVec<2> {
 };
 __device__ __forceinline__ double k1_sq(double o) { return o * o; }
 __device__ __forceinline__ double k1_sq(bb_d2 o) { return o.x * o.x + o.y * o.y; }
+__device__ __forceinline__ unsigned long long k1_abs(double o) { return abs_bits(o); }
+__device__ __forceinline__ unsigned long long k1_abs(bb_d2 o) {
+    return umax64(abs_bits(o.x), abs_bits(o.y));
+}
 
-template <bool ITER, bool ADD, bool REDUCE, int W = 1>
+// FX (fx_sums): |r| of the rows folded into rmax, as k1_finish
+template <bool ITER, bool ADD, bool REDUCE, int W = 1, bool FX = false>
 __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter, int64_t G,
                                                  int64_t r0, int64_t r1, double *part,
-                                                 unsigned *ticket) {
+                                                 unsigned *ticket,
+                                                 unsigned long long *rmax = nullptr) {
     typedef typename K1SumVec<W>::type vec;
     __shared__ double red[8];
     PH_DECL;
@@ -394,6 +469,7 @@ __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter
     PH(1);
     if (!BSLS_K1_SUM_EARLY) load(idx);
     double sq[1] = {0.0};
+    unsigned long long mb = 0ull;
     while (idx < ni) {
         const int64_t row = r0 + W * idx;
         vec o = v[0];
@@ -404,6 +480,7 @@ __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter
         if (ADD) o += tg;
         *reinterpret_cast<vec *>(&P.r[row]) = o;
         sq[0] += k1_sq(o);
+        if constexpr (FX) mb = umax64(mb, k1_abs(o));
         idx += gs;
         if (idx < ni) load(idx);
     }
@@ -414,8 +491,10 @@ __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter
         if (ADD) o += P.target[row];
         P.r[row] = o;
         sq[0] += o * o;
+        if constexpr (FX) mb = umax64(mb, abs_bits(o));
     }
     PH(2);
+    if constexpr (FX) rmax_fold(rmax, mb);
     if (!REDUCE) {
         PH_FLUSH(PH_SUM);
         return;
@@ -454,9 +533,16 @@ __global__ __launch_bounds__(256) void bb_k1_init(bsls_bb_problem P, int64_t r0,
 #ifndef BSLS_K1T_WGS
 #define BSLS_K1T_WGS 1
 #endif
-template <int MODE, bool ITER, bool ADD, bool REDUCE, bool ATOM = false>
+// FX (bsls_bb_problem.fx_sums, dealt images, never ATOM): the walk keeps each
+// row's sum in two integer words (tiles.hpp fx_add: order-free), scaled from
+// the caller's bound fx_a1 * x_bound; each row is converted once after the
+// walk, and what follows -- the finish, or the partials and bb_k1_sum -- is the
+// float form's, already ordered.
+template <int MODE, bool ITER, bool ADD, bool REDUCE, bool ATOM = false, bool FX = false>
 __global__ __launch_bounds__(1024, BSLS_K1T_WGS) void bb_k1t(bsls_bb_problem P, int64_t iter, unsigned *tkrb,
-                                               double *part, unsigned *ticket, int64_t rb_base) {
+                                               double *part, unsigned *ticket, int64_t rb_base,
+                                               unsigned long long *rmax = nullptr) {
+    static_assert(!(FX && ATOM), "the fixed-point sums finish through the ordered partials");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double red[32];   // (k1_finish: 2 doubles per wave)
     __shared__ int row_last;
@@ -474,25 +560,36 @@ __global__ __launch_bounds__(1024, BSLS_K1T_WGS) void bb_k1t(bsls_bb_problem P, 
                             threadIdx.x, blockDim.x);
         return;
     }
-    const int HR = (int)tile_lds_doubles(T, false);
+    const int HR = (int)tile_lds_doubles(T, FX);   // (FX: two words per row)
+    double fxs = 1.0, inv = 1.0;
+    bool bad = false;
+    if constexpr (FX) bad = fx_scale(P.fx_a1 * P.x_bound, fxs, inv);
     // (the clear and its barrier: under the dealt walk's first loads, tiles.hpp
     // BSLS_WALK_PREFILL)
     PH(1);
     auto clear = [&]() {
         PH(2);
-        for (int i = threadIdx.x; i < HR; i += blockDim.x) lds[i] = 0.0;
+        for (int i = threadIdx.x; i < HR; i += blockDim.x) lds[i] = 0.0;   // (integer 0 too)
         __syncthreads();
         PH(3);
     };
-    tile_walk_any<MODE>(T, rb, g, P.x, lds, nullptr, 1.0, 1.0, clear);
+    tile_walk_any<MODE, FX>(T, rb, g, P.x, lds, nullptr, fxs, 1.0, clear);
     PH(4);
     __syncthreads();
     PH(5);
     const int64_t G = T.ngroups;
     const int64_t r0 = rb * T.H, r1 = (r0 + T.H < P.m) ? r0 + T.H : P.m;
+    if constexpr (FX) {
+        // each row's words to its double, in place (the low words sit past the rows)
+        const int lo_off = (int)(T.H + T.halo + 1);
+        const double inv_lo = ldexp(inv, -fx_lo_shift(T.cols));
+        for (int i = threadIdx.x; i < (int)(r1 - r0); i += blockDim.x)
+            lds[i] = fx_row(lds, i, lo_off, inv, inv_lo, bad);
+        __syncthreads();
+    }
     if (G == 1) {
-        k1_finish<ADD, REDUCE>(P, iter, ITER, rb, (unsigned)T.nrb, r0, r1, 1, lds, part, ticket,
-                               red);
+        k1_finish<ADD, REDUCE, FX>(P, iter, ITER, rb, (unsigned)T.nrb, r0, r1, 1, lds, part,
+                                   ticket, red, rmax);
         PH(6);
         PH_FLUSH(PH_K1);
         return;
@@ -543,8 +640,8 @@ __global__ __launch_bounds__(1024, BSLS_K1T_WGS) void bb_k1t(bsls_bb_problem P, 
     __syncthreads();
     if (!row_last) return;
     __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    k1_finish<ADD, REDUCE>(P, iter, ITER, rb, (unsigned)T.nrb, r0, r1, G, nullptr, part, ticket,
-                           red);
+    k1_finish<ADD, REDUCE, FX>(P, iter, ITER, rb, (unsigned)T.nrb, r0, r1, G, nullptr, part,
+                               ticket, red, rmax);
 }
 
 // K2's epilogue rows per thread per batch (K2E; round 6: 4 -- C3's 3.8 rows
@@ -597,12 +694,19 @@ __device__ __forceinline__ void k2_stopped_sums(const bsls_bb_problem &P) {
 // adds them in group order and runs the epilogue -- no tickets.  Its slice of
 // ||r||^2 stays inside its own link range (rows of r the earlier parts'
 // exchanges have not finished may not be read).
-template <int MODE, bool ITER, int FUSE = 0, int CV = 0>
+// FX (bsls_bb_problem.fx_sums: gsel < 0, FUSE 0, MODE 1 / 3, dealt images):
+// the walk's row sums in two integer words (tiles.hpp fx_add: order-free),
+// scaled from fx_a2 * max|r| (rmax: the slots K1's finish keeps); after the
+// walk the rows -- the halo row too -- are converted in place to doubles (one
+// group of a scaled incidence: to w_i = colv_i * sum, the epilogue's product),
+// and the group hand-off and the N' epilogue run as in the float form.
+template <int MODE, bool ITER, int FUSE = 0, int CV = 0, bool FX = false>
 __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *__restrict__ dzv,
                                                const double *__restrict__ gp,
                                                double *__restrict__ gout, double *part,
                                                unsigned *ticket, unsigned *tk2rb, int64_t iter,
-                                               int gsel) {
+                                               int gsel, const unsigned long long *rmax = nullptr) {
+    static_assert(!FX || (FUSE == 0 && (MODE == 1 || MODE == 3)), "FX: the single-GCD dealt K2");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double red[5 * 16];
     __shared__ int row_last;
@@ -665,15 +769,28 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
         for (int i = threadIdx.x; i < HR; i += blockDim.x) {
             rows[i] = 0.0;
             if (MODE == 2) rc[i] = (i < nloc) ? colv_t<CV>(P, i0 + i) : 0.0;
+            if (FX) rc[i] = 0.0;   // (the low words: integer 0)
         }
         __syncthreads();
         PH(3);
     };
-    if (P.r_fx > 0.0)
+    if constexpr (FX) {
+        double fxs, inv;
+        const bool bad = fx_scale(P.fx_a2 * rmax_of(rmax), fxs, inv);
+        tile_walk_any<(MODE == 3 ? 0 : MODE), true>(T, rb, g, P.r, rows, rc, fxs, 1.0, clear);
+        PH(4);
+        __syncthreads();
+        const double inv_lo = ldexp(inv, -fx_lo_shift(T.cols));
+        for (int i = threadIdx.x; i < (int)nloc; i += blockDim.x) {
+            const double v = fx_row(rows, i, HR, inv, inv_lo, bad);
+            rows[i] = (MODE == 3 && G == 1) ? colv_t<CV>(P, i0 + i) * v : v;
+        }
+    } else if (P.r_fx > 0.0) {
         tile_walk_any<(MODE == 3 ? 0 : MODE), false, true>(T, rb, g, P.r, rows, rc, 1.0,
                                                             1.0 / P.r_fx, clear);
-    else
+    } else {
         tile_walk_any<(MODE == 3 ? 0 : MODE)>(T, rb, g, P.r, rows, rc, 1.0, 1.0, clear);
+    }
     PH(4);
     __syncthreads();
     PH(5);
@@ -689,7 +806,8 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
     // dealt image, one group (MODE 3): w_i = colv_i * (sum of r over row i),
     // one product per row (the sums' order is not fixed anyway), formed in the
     // epilogue below; several groups: by the finishing workgroup
-    const bool scale_epi = MODE == 3 && G == 1;
+    // (FX: the conversion above formed the products already)
+    const bool scale_epi = !FX && MODE == 3 && G == 1;
     if (G > 1 && gsel >= 0) {
         // the part pipeline: fixed roles (see above)
         if (gsel < G - 1) {
@@ -1065,11 +1183,15 @@ void bb_k3(bsls_bb_problem P, int64_t iter,
                                              double *__restrict__ zn,
                                              double *__restrict__ dzo,
                                              int32_t *__restrict__ wsc, int rec,
-                                             uint64_t *__restrict__ hd, int kinit) {
+                                             uint64_t *__restrict__ hd, int kinit,
+                                             unsigned long long *rmax_clear = nullptr) {
     PH_DECL;
     PH(0);
     const double sc[4] = {P.scal[BSLS_S_STOP], P.scal[BSLS_S_SUMDG], P.scal[BSLS_S_DZDG],
                           P.scal[BSLS_S_DGDG]};
+    // fx_sums: K2, which read max|r|, has finished and the next K1 finish has
+    // not begun: the slots back to 0 for it
+    if (rmax_clear && blockIdx.x == 0 && threadIdx.x < RMAX_SLOTS) rmax_clear[threadIdx.x] = 0ull;
     // kinit (stage 15): the next K1's r initialisation folded in (its atomic
     // group sums add into r): r = target on the shard_role 1 rank, 0 on the
     // others; once stopped, role 1 keeps its r and the others write 0 -- as
@@ -1371,6 +1493,34 @@ static bool k1_init_folded(const bsls_bb_problem &P) {
     return P.At.ent && P.At.ngroups > 1 && k1_atomic(P, false);
 }
 
+// K1 with fixed-point row sums (bsls_bb_problem.fx_sums): bb_k1t's FX form and,
+// with several groups, bb_k1_sum's -- the launches of the float form
+template <int MODE, bool REDUCE, bool ITER>
+static void launch_k1t_fx(const bsls_bb_problem &P, int64_t iter, const BBWork &w,
+                          hipStream_t st, int64_t rb0, int64_t rb1) {
+    allow_lds(bb_k1t<MODE, ITER, true, REDUCE, false, true>);
+    bb_k1t<MODE, ITER, true, REDUCE, false, true><<<(int)((rb1 - rb0) * P.At.ngroups),
+                                                    BSLS_TILE_THREADS,
+                                                    tile_lds_doubles(P.At, true) * 8, st>>>(
+        P, iter, w.tkrb, w.p1, w.tk1, rb0, w.rmax);
+    if (!(BSLS_K1_SPLIT && P.At.ngroups > 1)) return;
+    const int64_t r0 = rb0 * P.At.H, r1 = (rb1 * P.At.H < P.m) ? rb1 * P.At.H : P.m;
+    constexpr int K1_SUM_GRID = 1024;
+    const bool pairs = BSLS_K1_SUM_PAIRS && !(P.m & 1) && !(r0 & 1) && r1 - r0 >= 2 &&
+                       !(((uintptr_t)P.rpart | (uintptr_t)P.target | (uintptr_t)P.r) & 15);
+    if (pairs) {
+        const int gk = grid_for((r1 - r0) / 2, 256);
+        bb_k1_sum<ITER, true, REDUCE, 2, true><<<(REDUCE && gk > K1_SUM_GRID) ? K1_SUM_GRID : gk,
+                                                 256, 0, st>>>(P, iter, P.At.ngroups, r0, r1, w.pf,
+                                                               w.tkf, w.rmax);
+        return;
+    }
+    const int gk = grid_for(r1 - r0, 256);
+    bb_k1_sum<ITER, true, REDUCE, 1, true><<<(REDUCE && gk > K1_SUM_GRID) ? K1_SUM_GRID : gk, 256,
+                                             0, st>>>(P, iter, P.At.ngroups, r0, r1, w.pf, w.tkf,
+                                                      w.rmax);
+}
+
 template <int MODE, bool ADD, bool REDUCE, bool ITER>
 static void launch_k1t_mode(const bsls_bb_problem &P, int64_t iter, const BBWork &w,
                             hipStream_t st, int64_t rb0, int64_t rb1, bool skip_init) {
@@ -1390,6 +1540,16 @@ static void launch_k1t_mode(const bsls_bb_problem &P, int64_t iter, const BBWork
             bb_r_finish<<<(grid_for(P.m, 256) < R_FINISH_GRID ? grid_for(P.m, 256) : R_FINISH_GRID),
                           256, 0, st>>>(P, iter, w.pf, w.tkf, 0);
         return;
+    }
+    if constexpr (ADD && (REDUCE || !ITER)) {
+        // fx_sums (check_problem: dealt images, never the atomic K1; the entry
+        // points that take the other forms -- no target, or an iteration's K1
+        // without the reduction -- reject such a problem): the fixed-point
+        // walk, and the finish that keeps max|r|
+        if (P.fx_sums) {
+            launch_k1t_fx<MODE, REDUCE, ITER>(P, iter, w, st, rb0, rb1);
+            return;
+        }
     }
     allow_lds(bb_k1t<MODE, ITER, ADD, REDUCE>);
     bb_k1t<MODE, ITER, ADD, REDUCE><<<(int)((rb1 - rb0) * P.At.ngroups), BSLS_TILE_THREADS,
@@ -1441,6 +1601,16 @@ template <int MODE, bool ITER, int FUSE, int CV>
 static void launch_k2t_cv(const bsls_bb_problem &P, const double *gp, double *gout,
                           const BBWork &w, hipStream_t st, int64_t iter, const double *dz,
                           int gsel) {
+    if constexpr (FUSE == 0 && (MODE == 1 || MODE == 3)) {
+        // fx_sums (check_problem: a dealt image; bsls_bb_k2_part rejects it)
+        if (P.fx_sums && gsel < 0) {
+            allow_lds(bb_k2t<MODE, ITER, 0, CV, true>);
+            bb_k2t<MODE, ITER, 0, CV, true><<<(int)(P.ATt.nrb * P.ATt.ngroups), BSLS_TILE_THREADS,
+                                              tile_lds_doubles(P.ATt, true) * 8, st>>>(
+                P, dz, gp, gout, w.p2, w.tk2, w.tk2rb, iter, gsel, w.rmax);
+            return;
+        }
+    }
     allow_lds(bb_k2t<MODE, ITER, FUSE, CV>);
     bb_k2t<MODE, ITER, FUSE, CV><<<(int)(gsel >= 0 ? P.ATt.nrb : P.ATt.nrb * P.ATt.ngroups),
                                    BSLS_TILE_THREADS, tile_lds_doubles(P.ATt, MODE == 2) * 8, st>>>(
@@ -1492,12 +1662,13 @@ static void launch_k3_cv(const bsls_bb_problem &P, int64_t iter, const double *z
     // (bsls_bb_problem.pava_warm; a second set of masks for a second
     // projection whose inputs alternate with the first's)
     uint64_t *hd = P.pava_warm ? w.hd + (slot ? w.hd_stride : 0) : nullptr;
+    unsigned long long *rmc = P.fx_sums ? w.rmax : nullptr;
     if (k3_merge(P))
         bb_k3<2, true, CV><<<grid_for(P.npacks, 8), 256, 0, st>>>(P, iter, zc, g, zn, w.dz, w.wsc,
-                                                                   rec, hd, kinit);
+                                                                   rec, hd, kinit, rmc);
     else
         bb_k3<1, false, CV><<<grid_for(P.npacks, 4), 256, 0, st>>>(P, iter, zc, g, zn, w.dz,
-                                                                    w.wsc, rec, hd, kinit);
+                                                                    w.wsc, rec, hd, kinit, rmc);
 }
 
 static void launch_k3(const bsls_bb_problem &P, int64_t iter, const double *zc, const double *g,
@@ -1541,6 +1712,20 @@ static int check_problem(const bsls_bb_problem *p) {
     // the reference's exact-zero sum(delta_g) exit fires, BB.py:22)
     if (p->sy_dr != 0) return BSLS_E_ARG;
     const bool general = p->colv == nullptr;
+    if (p->fx_sums) {
+        // fixed-point row sums: dealt images of both matrices with room for two
+        // words per row, the whole problem on this GCD, ordered group sums, and
+        // bounds a scale can be made from
+        const auto bound = [](double v) { return v > 0.0 && v <= 1e300; };
+        if (p->fx_sums != 1 || p->shard_role != 0 || p->r_fx != 0.0 || p->k1_atomic == 2)
+            return BSLS_E_ARG;
+        if (!p->At.ent || (p->At.layout & 3) == 0 || !p->ATt.ent || (p->ATt.layout & 3) == 0)
+            return BSLS_E_ARG;
+        if (!tiles_valid(p->At, p->m, p->n, 0, general, true, PANEL_LDS_MAX) ||
+            !tiles_valid(p->ATt, p->n, p->m, 1, general, true, PANEL_LDS_MAX))
+            return BSLS_E_ARG;
+        if (!bound(p->fx_a1) || !bound(p->fx_a2) || !bound(p->x_bound)) return BSLS_E_ARG;
+    }
     if (p->At.ent) {
         if (!tiles_valid(p->At, p->m, p->n, 0, general, false, PANEL_LDS_MAX)) return BSLS_E_ARG;
         if (p->At.ngroups > 1 && !p->rpart) return BSLS_E_ARG;
@@ -1563,6 +1748,13 @@ static int check_problem(const bsls_bb_problem *p) {
     if (p->long_packs && (p->nlong < 0 || (p->nlong > 0 && (!p->long_off || !p->long_scratch))))
         return BSLS_E_ARG;
     return BSLS_OK;
+}
+
+// the entry points that fx_sums does not cover (include/bsls_hip.h)
+static int check_problem_float(const bsls_bb_problem *p) {
+    const int rc = check_problem(p);
+    if (rc != BSLS_OK) return rc;
+    return p->fx_sums ? BSLS_E_ARG : BSLS_OK;
 }
 
 // ---- LBFGS.solve's weak Wolfe line search on the device -------------------------
@@ -1842,7 +2034,7 @@ extern "C" size_t bsls_dore_work_size(int64_t nz, int64_t m) {
 
 extern "C" int bsls_dore_iterate(const bsls_bb_problem *p, const bsls_dore_state *d,
                                  int64_t first_iter, int64_t count, void *stream) {
-    const int rc = check_problem(p);
+    const int rc = check_problem_float(p);
     if (rc != BSLS_OK) return rc;
     if (!d || first_iter < 0 || count < 0 || !d->X1 || !d->D || !d->X2 || !d->AX2 || !d->err ||
         !d->b || !d->S || !d->S2 || !d->dsc || !d->part || !d->tickets)
@@ -1910,7 +2102,7 @@ static int check_ls(const bsls_ls_state *s) {
 }
 
 extern "C" int bsls_lbfgs_ls_begin(const bsls_bb_problem *p, const bsls_ls_state *s, void *stream) {
-    int rc = check_problem(p);
+    int rc = check_problem_float(p);
     if (rc != BSLS_OK || (rc = check_ls(s)) != BSLS_OK) return rc;
     constexpr int LS_GRID = 512;
     const int g = grid_for(p->nz, 256);
@@ -1922,7 +2114,7 @@ extern "C" int bsls_lbfgs_ls_begin(const bsls_bb_problem *p, const bsls_ls_state
 
 extern "C" int bsls_lbfgs_ls_trials(const bsls_bb_problem *p, const bsls_ls_state *s,
                                     int64_t count, void *stream) {
-    int rc = check_problem(p);
+    int rc = check_problem_float(p);
     if (rc != BSLS_OK || (rc = check_ls(s)) != BSLS_OK) return rc;
     if (count < 0) return BSLS_E_ARG;
     hipStream_t st = (hipStream_t)stream;
@@ -1950,7 +2142,7 @@ extern "C" int bsls_lbfgs_ls_trials(const bsls_bb_problem *p, const bsls_ls_stat
 
 extern "C" int bsls_lbfgs_ls_finish(const bsls_bb_problem *p, const bsls_ls_state *s,
                                     double *y_out, double *s_out, void *stream) {
-    int rc = check_problem(p);
+    int rc = check_problem_float(p);
     if (rc != BSLS_OK || (rc = check_ls(s)) != BSLS_OK) return rc;
     constexpr int LS_GRID = 512;
     const int g = grid_for(p->nz, 256);
@@ -1990,6 +2182,12 @@ extern "C" size_t bsls_bb_dz_offset(int64_t m, int64_t n, int64_t nz) {
     return (size_t)((char *)bb_layout(nullptr, m, n, nz).dz - (char *)nullptr);
 }
 
+extern "C" size_t bsls_bb_rmax_offset(int64_t m, int64_t n, int64_t nz) {
+    return (size_t)((char *)bb_layout(nullptr, m, n, nz).rmax - (char *)nullptr);
+}
+
+extern "C" int bsls_bb_rmax_slots(void) { return RMAX_SLOTS; }
+
 extern "C" int bsls_bb_stage(const bsls_bb_problem *p, int stage, int64_t iter, void *stream) {
     const int rc = check_problem(p);
     if (rc != BSLS_OK) return rc;
@@ -1997,10 +2195,14 @@ extern "C" int bsls_bb_stage(const bsls_bb_problem *p, int stage, int64_t iter, 
     hipStream_t st = (hipStream_t)stream;
     const BBWork w = bb_layout(P);
     const int zc = (int)((iter - 1) & 1), zn = (int)(iter & 1);
+    // fx_sums: the single-GCD stages only (0, 3-7, 9)
+    if (P.fx_sums && (stage == 1 || stage == 2 || stage == 8 || (stage >= 10 && stage <= 15)))
+        return BSLS_E_ARG;
     switch (stage) {
         case 0:  // reset scalars and tickets
             BSLS_CHECK(hipMemsetAsync(P.scal, 0, BSLS_S_COUNT * sizeof(double), st));
             BSLS_CHECK(hipMemsetAsync(P.work, 0, (size_t)((char *)w.p1 - (char *)P.work), st));
+            if (P.fx_sums) BSLS_CHECK(hipMemsetAsync(w.rmax, 0, RMAX_SLOTS * 8, st));
             return BSLS_OK;
         case 1:  // r_partial = A_g x_g (+ target on the shard_role 1 rank)
             if (P.shard_role == 1) {
@@ -2060,6 +2262,8 @@ extern "C" int bsls_bb_stage(const bsls_bb_problem *p, int stage, int64_t iter, 
             bb_z2x<<<grid_for(P.n, 256), 256, 0, st>>>(P, P.z[0]);
             break;
         case 7:  // single GCD K1: r = A x + target, ||r||^2, stop test (iter > 0)
+            // (fx_sums: outside an iteration no K3 has cleared max|r| for this finish)
+            if (P.fx_sums && iter <= 0) BSLS_CHECK(hipMemsetAsync(w.rmax, 0, RMAX_SLOTS * 8, st));
             if (iter > 0) launch_k1<true, true, true>(P, iter, w, st);
             else launch_k1<true, true, false>(P, iter, w, st);
             break;
@@ -2080,7 +2284,7 @@ extern "C" int64_t bsls_bb_row_blocks(const bsls_bb_problem *p, int64_t *rows_pe
 
 extern "C" int bsls_bb_residual_rows(const bsls_bb_problem *p, int64_t iter, int64_t rb0,
                                      int64_t rb1, void *stream) {
-    const int rc = check_problem(p);
+    const int rc = check_problem_float(p);
     if (rc != BSLS_OK) return rc;
     const bsls_bb_problem &P = *p;
     if (rb0 < 0 || rb1 <= rb0 || rb1 > k1_row_blocks(P)) return BSLS_E_ARG;
@@ -2110,6 +2314,8 @@ extern "C" int bsls_bb_prologue(const bsls_bb_problem *p, void *stream) {
     BSLS_LAUNCH_CHECK();
     if ((e = bsls_bb_stage(p, 3, 0, stream)) != BSLS_OK) return e;  // g_prev -> g[0]
     if ((e = bsls_bb_stage(p, 6, 0, stream)) != BSLS_OK) return e;
+    // (fx_sums: max|r| of r(z0 + 1) was K2's; r(z0)'s alone is iteration 1's)
+    if (P.fx_sums) BSLS_CHECK(hipMemsetAsync(w.rmax, 0, RMAX_SLOTS * 8, st));
     launch_k1<true, true, false>(P, 0, w, st);  // r(z0), f(z0)
     BSLS_LAUNCH_CHECK();
     return BSLS_OK;
@@ -2138,7 +2344,7 @@ extern "C" int bsls_bb_iterate(const bsls_bb_problem *p, int64_t first_iter, int
 // bsls_bb_shard_iterate_parts drives them with the exchange of each part's
 // rows of r on a second stream)
 extern "C" int bsls_bb_k2_part(const bsls_bb_problem *p, int64_t iter, int part, void *stream) {
-    const int rc = check_problem(p);
+    const int rc = check_problem_float(p);
     if (rc != BSLS_OK) return rc;
     const bsls_bb_problem &P = *p;
     if (iter <= 0 || !P.ATt.ent || (P.ATt.layout & 3) == 0 || P.ATt.ngroups < 2 || part < 0 ||
@@ -2154,7 +2360,7 @@ extern "C" int bsls_bb_k2_part(const bsls_bb_problem *p, int64_t iter, int part,
 
 extern "C" int bsls_bb_k1_rows(const bsls_bb_problem *p, int64_t iter, int64_t rb0, int64_t rb1,
                                void *stream) {
-    const int rc = check_problem(p);
+    const int rc = check_problem_float(p);
     if (rc != BSLS_OK) return rc;
     const bsls_bb_problem &P = *p;
     if (iter <= 0 || rb0 < 0 || rb1 <= rb0 || rb1 > k1_row_blocks(P)) return BSLS_E_ARG;

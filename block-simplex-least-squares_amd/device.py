@@ -874,6 +874,43 @@ class BlockLayout:
         return plan
 
 
+def fixed_sum_bounds(A, AT, scaled):
+    """(fx_a1, fx_a2) of bsls_bb_problem.fx_sums: per unit of the gathered
+    vector's max, a bound on the sum of |terms| of any row -- the longest row
+    for a scaled incidence (K1 gathers colv * x, K2 scales each row sum once:
+    every term is a gathered entry), else the largest row sum of |values|;
+    fx_a1 over the rows of A (K1), fx_a2 over those of A' (K2)."""
+    def one(M):
+        M = sps.csr_matrix(M)
+        if M.nnz == 0:
+            return 1.0
+        if scaled:
+            return float(max(1, int(np.max(np.diff(M.indptr)))))
+        return float(max(np.max(np.asarray(abs(M).sum(axis=1)).ravel()), 1e-300))
+    return one(A), one(AT)
+
+
+def fixed_sums_check(deterministic, tile_layouts, fmt, link_parts):
+    """The engine choices fixed_sums cannot be combined with (ValueError)."""
+    if deterministic:
+        raise ValueError('fixed_sums and deterministic are two ways to the same end: choose one')
+    lay = tile_layouts
+    if lay is None and os.environ.get('BSLS_TILE_LAYOUT'):
+        lay = tuple(int(v) for v in os.environ['BSLS_TILE_LAYOUT'].split(','))
+    if lay is not None and not (lay[0] in (1, 2) and lay[1] in (1, 2)):
+        raise ValueError('fixed_sums needs the dealt tile layouts (1 or 2) for K1 and K2')
+    if (fmt or os.environ.get('BSLS_SPMV_FORMAT') or 'auto') == 'panels':
+        raise ValueError("fixed_sums needs tile images: fmt='panels' has none")
+    if link_parts is not None and int(link_parts) > 1:
+        raise ValueError('fixed_sums does not cover link parts')
+
+
+def fixed_plan_fits(plan, halo):
+    """Whether a tile plan (H, groups, order) leaves the LDS room for the two
+    words per row of the fixed-point sums."""
+    return 2 * (int(plan[0]) + halo + 1) * 8 <= _native.TILE_LDS_BYTES
+
+
 class BBEngine:
     """Fused z-space projected BB (python/BB.py:7-45 over python/main.py:53-65).
 
@@ -886,7 +923,21 @@ class BBEngine:
     def __init__(self, A, b, block_sizes, options=None, early_exit=True, A_dev=None,
                  AT_dev=None, AT=None, target=None, x0=None, general=False, fmt=None,
                  tile_plans=(None, None), colv=None, deterministic=False, tile_layouts=None,
-                 link_parts=None):
+                 link_parts=None, fixed_sums=None):
+        # fixed_sums: order-free fixed-point row sums on the dealt tiles
+        # (bsls_bb_problem.fx_sums) -- bit-reproducible iterates and exit
+        # iterations from the default engine's walks.  None reads
+        # BSLS_FIXED_SUMS (1 = on) for the whole-problem default engine; the
+        # engines built for something else (deterministic, link parts, a column
+        # shard's target) do not take the default.  Checked before anything
+        # touches the device.
+        if fixed_sums is None:
+            fixed_sums = (os.environ.get('BSLS_FIXED_SUMS', '0') not in ('', '0')
+                          and not deterministic and target is None
+                          and not (link_parts is not None and int(link_parts) > 1))
+        self.fixed_sums = bool(fixed_sums)
+        if self.fixed_sums:
+            fixed_sums_check(deterministic, tile_layouts, fmt, link_parts)
         torch = _torch()
         L = _native.lib()
         self.layout = lay = BlockLayout(block_sizes)
@@ -923,6 +974,20 @@ class BBEngine:
         self.fmt_A = spmv_format(A, fmt, dealt=tile_layouts[0] in (1, 2))
         self.fmt_AT = spmv_format(AT, fmt, dealt=tile_layouts[1] in (1, 2))
         self.A_pan = self.AT_pan = self.A_til = self.AT_til = None
+        if self.fixed_sums:
+            # two words per row: plans for half the rows per block (as
+            # DeviceLSQ's tiles_fixed); a caller's plan must leave that room
+            tile_plans = (
+                tile_plans[0] or tile_plan(self.m, self.n, 0, colv_lds=True,
+                                           env='BSLS_TILE_PLAN_A', layout=tile_layouts[0],
+                                           nnz=A.nnz),
+                tile_plans[1] or tile_plan(self.n, self.m, 1, colv_lds=True,
+                                           env='BSLS_TILE_PLAN_AT', layout=tile_layouts[1],
+                                           nnz=AT.nnz))
+            for plan, halo, name in ((tile_plans[0], 0, 'K1'), (tile_plans[1], 1, 'K2')):
+                if not fixed_plan_fits(plan, halo):
+                    raise ValueError('fixed_sums: the %s tile plan H = %d leaves no room for two '
+                                     'words per row in the LDS' % (name, plan[0]))
         if self.fmt_A == 'panels':
             prow, groups = k1_plan(self.m)
             try:
@@ -1066,10 +1131,20 @@ class BBEngine:
         for field, env in (('k1_atomic', 'BSLS_K1_ATOMIC'), ('k3_merge', 'BSLS_K3_MERGE')):
             v = os.environ.get(env)
             setattr(P, field, 0 if v is None else (2 if int(v) else 1))
+        if self.fixed_sums:
+            if P.k1_atomic == 2:
+                raise ValueError('fixed_sums keeps the ordered group sums: BSLS_K1_ATOMIC=1 '
+                                 'does not go with it')
+            P.fx_sums = 1
+            P.fx_a1, P.fx_a2 = fixed_sum_bounds(A, AT, self.scaled)
+            P.x_bound = self.colv_max
+            self._rmax_off = int(L.bsls_bb_rmax_offset(self.m, self.n, self.nz))
         self.P = P
         self.z0 = None
         if xin is not None:
             self.x.copy_(self.colv * xin if self.scaled else xin)
+            if self.fixed_sums:
+                self.set_x_bound(float(self.x.abs().max().item()))
             self.stage(7, 0)                       # r = A x0 + (-b)
             self.target.copy_(self.r)
 
@@ -1094,10 +1169,37 @@ class BBEngine:
         self.z[0][:self.nz].copy_(z0)
         self.z0 = z0
 
+    def set_x_bound(self, bound):
+        """fixed_sums: the bound on |entries of x as K1 gathers them| for the
+        calls enqueued next (bsls_bb_problem.x_bound; colv_max in iterations)."""
+        self.P.x_bound = max(float(bound), 1e-300)
+
+    def load_r(self, r):
+        """Copy a residual into r as a K1 finish would leave it: under
+        fixed_sums also max|r| in the workspace slots K2 scales from."""
+        torch = _torch()
+        self.r.copy_(torch.as_tensor(r, dtype=torch.float64).reshape(-1))
+        if self.fixed_sums:
+            n = _native.lib().bsls_bb_rmax_slots()
+            slots = self.work[self._rmax_off:self._rmax_off + 8 * n].view(torch.float64)
+            slots.zero_()
+            slots[0] = self.r.abs().max()      # (the bit pattern the kernels' atomic max keeps)
+
+    def _fixed_only_bb(self, what):
+        if self.fixed_sums:
+            raise ValueError('%s is not covered by fixed_sums (BB only): build the engine '
+                             'without it' % what)
+
     def prologue(self):
+        if self.fixed_sums:
+            # x = N (z0 + 1), then N z0: differences of two entries
+            zmax = float(self.z[0][:self.nz].abs().max().item()) if self.nz else 0.0
+            self.set_x_bound(2.0 * (zmax + 1.0) * self.colv_max)
         check(_native.lib().bsls_bb_prologue(self.P, stream_handle()), 'bsls_bb_prologue')
 
     def iterate(self, first, count):
+        if self.fixed_sums:
+            self.P.x_bound = self.colv_max        # |N z| <= 1 after K3's clip
         check(_native.lib().bsls_bb_iterate(self.P, int(first), int(count), stream_handle()),
               'bsls_bb_iterate')
 
@@ -1131,6 +1233,8 @@ class BBEngine:
         groups and ranks land.  Every |partial sum of r| must stay below
         2^62 / scale (distributed.ShardedBB sizes it)."""
         scale = float(scale)
+        if scale > 0:
+            self._fixed_only_bb('a fixed-point r')
         if scale < 0 or (scale > 0 and not self.fixed_r_ok()):
             raise ValueError('fixed-point r needs an atomic sharded K1 (fixed_r_ok)')
         self.P.r_fx = scale
@@ -1154,6 +1258,8 @@ class BBEngine:
         (distributed.ShardedBB)."""
         if role not in (0, 1, 2):
             raise ValueError('shard role must be 0, 1 or 2')
+        if role != 0:
+            self._fixed_only_bb('a column shard')
         self.P.shard_role = int(role)
 
     def row_blocks(self):
@@ -1212,17 +1318,20 @@ class BBEngine:
         if z.numel() != self.nz:
             raise ValueError('z has %d entries, expected %d' % (z.numel(), self.nz))
         self.z[0][:self.nz].copy_(z)
+        if self.fixed_sums:
+            self.set_x_bound(2.0 * float(z.abs().max().item()) * self.colv_max if self.nz else 0.0)
         self.stage(6, 0)
 
     def apply_A(self, z, alpha=1.0):
         """alpha A N z (DORE's linop with A scaled by alpha, gradient_descent.py:57-63)."""
+        self._fixed_only_bb('apply_A (DORE)')
         self._x_of(z)
         self.stage(1, 0)
         return self.r * alpha if alpha != 1.0 else self.r.clone()
 
     def apply_AT(self, r, alpha=1.0):
         """alpha N' A' r (DORE's linop_T)."""
-        self.r.copy_(r)
+        self.load_r(r)
         self.stage(3, 0)
         g = self.g[0][:self.nz]
         return g * alpha if alpha != 1.0 else g.clone()
@@ -1248,6 +1357,7 @@ class BBEngine:
 
     def line_search(self):
         """This engine's device weak Wolfe line search (LBFGS.solve)."""
+        self._fixed_only_bb('the line search')
         ls = getattr(self, '_ls', None)
         if ls is None:
             ls = self._ls = LineSearch(self)
@@ -1257,6 +1367,9 @@ class BBEngine:
         """A x for an x-space vector (LS_postprocess's A x_true)."""
         torch = _torch()
         x = torch.as_tensor(x, dtype=torch.float64, device='cuda').reshape(-1)
+        if self.fixed_sums:
+            # (the stage without target is not covered: the general CSR kernel)
+            return self.A.matvec(x)
         self.x.copy_(self.colv * x if self.scaled else x)
         self.stage(1, 0)
         return self.r.clone()

@@ -60,6 +60,9 @@ class GradientDescent:
     def run(self):
         logging.debug('Starting %s solver...' % self.method)
         e = self.engine
+        if e is not None and getattr(e, 'fixed_sums', False) and self.method != 'BB':
+            raise ValueError('method %r does not run on a fixed_sums (reproducible) engine: '
+                             'BB only' % self.method)
         if self.method == 'LBFGS':
             f, nabla_f, proj = self._device_closures() if e else (self.f, self.nabla_f, self.proj)
             z0 = self._z0_device() if e else self.z0

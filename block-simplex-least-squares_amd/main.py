@@ -36,9 +36,14 @@ def parser():
     p.add_argument('--device', dest='device', choices=['gpu', 'cpu'], default=None,
                    help='gpu (default: the MI355X engine) or cpu (the reference\'s own path: '
                         'SciPy closures + the host c_extensions library; also BSLS_DEVICE=cpu)')
-    p.add_argument('--deterministic', dest='deterministic', action='store_true', default=None,
-                   help='fixed-order SpMV sums (bit-reproducible runs and exit iterations); '
-                        'also BSLS_DETERMINISTIC=1')
+    how = p.add_mutually_exclusive_group()
+    how.add_argument('--deterministic', dest='deterministic', action='store_true', default=None,
+                     help='fixed-order SpMV sums (bit-reproducible runs and exit iterations); '
+                          'also BSLS_DETERMINISTIC=1')
+    how.add_argument('--reproducible', dest='reproducible', action='store_true', default=None,
+                     help='the default engine\'s dealt tiles with order-free fixed-point row '
+                          'sums (bit-reproducible runs and exit iterations, method BB only); '
+                          'also BSLS_FIXED_SUMS=1')
     return p
 
 
@@ -49,16 +54,19 @@ def deterministic_default():
     return os.environ.get('BSLS_DETERMINISTIC', '0') not in ('', '0')
 
 
-def build_engine(A, b, x0, block_sizes, options=None, deterministic=None):
+def build_engine(A, b, x0, block_sizes, options=None, deterministic=None, reproducible=None):
     """The device engine of solve_in_z's closures.  deterministic=True keeps
     every SpMV row sum in a fixed order (panels / thread-stream tiles): runs are
     bit-reproducible, so the exact-zero exit of BB.py:22 and the exit iteration
     repeat run to run; the default (dealt tiles, LDS atomic row sums) is faster
-    and reproducible to ~1e-16."""
+    and reproducible to ~1e-16.  reproducible=True keeps the dealt tiles and
+    sums their rows in fixed point instead (order-free: bit-reproducible too;
+    BB only); None leaves it to BSLS_FIXED_SUMS (BBEngine(fixed_sums=None))."""
     from device import BBEngine
     if deterministic is None:
-        deterministic = deterministic_default()
-    return BBEngine(A, b, block_sizes, options=options, x0=x0, deterministic=bool(deterministic))
+        deterministic = deterministic_default() and not reproducible
+    return BBEngine(A, b, block_sizes, options=options, x0=x0, deterministic=bool(deterministic),
+                    fixed_sums=(True if reproducible else None))
 
 
 def solve_in_z(A, b, x0, N, block_sizes, method, options=None, engine=None, deterministic=None):
@@ -224,6 +232,11 @@ def LS_postprocess(states, x0, A, b, x_true, scaling=None, block_sizes=None, out
 def main(args=None, plot=False):
     if args is None:
         args = parser().parse_args()
+    reproducible = getattr(args, 'reproducible', None)
+    if reproducible and args.method != 'BB':
+        raise ValueError('--reproducible covers --method BB only (got %r)' % args.method)
+    if reproducible and getattr(args, 'deterministic', None):
+        raise ValueError('--reproducible and --deterministic exclude each other')
     if args.log in ACCEPTED_LOG_LEVELS:
         logging.basicConfig(level=getattr(logging, args.log))
     config = {'full': True, 'L': True, 'OD': True, 'CP': True, 'LP': True,
@@ -246,7 +259,8 @@ def main(args=None, plot=False):
                                                    block_sizes=block_sizes, N=N, output=output)
         return iters, times, states, output
     eng = build_engine(AA, bb, x0, block_sizes,
-                       deterministic=getattr(args, 'deterministic', None))
+                       deterministic=getattr(args, 'deterministic', None),
+                       reproducible=reproducible)
     iters, times, states = solve_in_z(AA, bb, x0, N, block_sizes, args.method, engine=eng)
     x_last, error, output = LS_postprocess(states, x0, AA, bb, x_split, scaling=scaling,
                                            block_sizes=block_sizes, N=N, output=output,

@@ -396,12 +396,46 @@ typedef struct bsls_bb_problem {
      * retired in round 6; K2 sums dz . dg from K3's dz, the reference's
      * expression. */
     int64_t sy_dr;
+    /* 1: order-free row sums on the dealt tiles -- K1's and K2's walks keep
+     * each row's sum in two 64-bit integer words (csrc/tiles.hpp fx_add)
+     * instead of adding doubles with LDS atomics, and convert it once after
+     * the walk; everything downstream (group partials in group order, N', the
+     * reductions) is ordered already, so iterates and exit iterations repeat
+     * bit for bit.  Needs dealt images for both At and ATt whose plans leave
+     * room for two words per row (twice the LDS), shard_role 0, r_fx 0,
+     * k1_atomic != 2 and finite positive fx_a1 / fx_a2 / x_bound; anything
+     * else is BSLS_E_ARG.  K2's scale comes from max|r|, which the kernels that
+     * finish r keep in the workspace (an integer atomic max, order-free; K3
+     * clears it for the next K1).  A row whose integer sum leaves the range its
+     * bound allows (an entry beyond x_bound, a NaN or inf among the terms)
+     * comes out as NaN.
+     * Entry points that reject such a problem (BSLS_E_ARG): bsls_dore_iterate,
+     * bsls_lbfgs_ls_begin / _trials / _finish, bsls_bb_k2_part,
+     * bsls_bb_k1_rows, bsls_bb_residual_rows, bsls_bb_shard_iterate,
+     * bsls_bb_shard_iterate_parts, and bsls_bb_stage 1, 2, 8 and 10-15.
+     * 0: the float row sums. */
+    int64_t fx_sums;
+    /* fx_sums: a row's bound on sum |terms| per unit of the gathered vector's
+     * max -- fx_a1 for K1 (the max row nnz of A for a scaled incidence, else
+     * max_i sum_j |A_ij|), fx_a2 the same over the rows of A' for K2. */
+    double fx_a1, fx_a2;
+    /* fx_sums: a bound on |entries of x as K1 gathers them| (colv * N z for a
+     * scaled incidence), set by the caller for the calls it enqueues, as
+     * bsls_lsq_op.x_bound: max|colv| in iterations (|N z| <= 1 after K3's
+     * clip), 2 (max|z0| + 1) max|colv| for the prologue. */
+    double x_bound;
 } bsls_bb_problem;
 
 size_t bsls_bb_workspace_size(int64_t m, int64_t n, int64_t nz);
 /* Byte offset in `work` of dz = z - z_prev (nz doubles), the hand-off K3 writes
  * for the next K2 (and the prologue for iteration 1); for tests and tools. */
 size_t bsls_bb_dz_offset(int64_t m, int64_t n, int64_t nz);
+/* fx_sums: byte offset in `work` of the bsls_bb_rmax_slots() 64-bit words
+ * that hold max|r| as the bit patterns of non-negative doubles (the max over
+ * the words counts; all 0 = none yet).  A caller that writes r itself, without
+ * a K1 finish, stores max|r| there before stage 3. */
+size_t bsls_bb_rmax_offset(int64_t m, int64_t n, int64_t nz);
+int bsls_bb_rmax_slots(void);
 /* Scratch bytes for K3's long blocks of `total` z entries in all. */
 size_t bsls_bb_long_scratch_size(int64_t total);
 /* BB.py:14-15 and the first f(z0): resets scal/tickets, g[0] = grad(z0 + 1),
