@@ -1450,8 +1450,15 @@ template <typename K>
 static void allow_lds(K kernel) {
     static bool done = false;
     if (!done) {
-        (void)hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
-                                  PANEL_LDS_MAX);
+        // A refusal must not stay behind as the thread's last error: the launch
+        // check after the kernel would report it as the launch's.  (PANEL_LDS_MAX
+        // on top of a kernel's static LDS can pass the CU's 160 KB -- bb_k2t's
+        // iterating forms hold 656 B -- and `done` is per kernel signature, so
+        // it is a process's first K2 on tiles that asks: stage 3 of an iteration
+        // with no prologue before it returned hipErrorInvalidValue.)
+        if (hipFuncSetAttribute((const void *)kernel, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                PANEL_LDS_MAX) != hipSuccess)
+            (void)hipGetLastError();
         done = true;
     }
 }
