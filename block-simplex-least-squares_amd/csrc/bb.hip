@@ -124,32 +124,19 @@ __device__ __forceinline__ double colv_t(const bsls_bb_problem &P, int64_t i) {
     else return P.colv[i];
 }
 
-// The hand-offs between the iteration's kernels, each change behind a switch
-// of its own (A/B variant builds: make VAR=_x DEFS=-DBSLS_K1_SUM_PAIRS=0 ...;
-// the measurements: profiles/handoff_ab.txt):
-//   BSLS_K1_SUM_EARLY  bb_k1_sum issues its first rows' loads before its stop
-//                      test resolves (one memory round trip instead of two)
-//   BSLS_K1_SUM_PAIRS  bb_k1_sum takes two adjacent rows per thread with 16-B
-//                      loads and stores where m and the first row are even
-//   BSLS_WT_RPART      the split K1's partials leave through write-through
-//                      stores (as K3's z / dz / x): no dirty lines for the
-//                      kernel's end to flush before bb_k1_sum starts
-//                      (the same for K2's g and bb_k1_sum's r measured
-//                      slower and is not in the source)
+// The hand-offs between the iteration's kernels (the measurements:
+// profiles/handoff_ab.txt): bb_k1_sum issues its first rows'
+// loads before its stop test resolves (one memory round trip instead of two)
+// and takes two adjacent rows per thread with 16-B loads and stores where m
+// and the first row are even; the split K1's partials leave through
+// write-through stores (as K3's z / dz / x): no dirty lines for the kernel's
+// end to flush before bb_k1_sum starts (the same for K2's g and bb_k1_sum's r
+// measured slower and is not in the source).  The forms these replaced, each
+// behind an A/B switch of its own, last existed at commit 36c7740.
 // BSLS_PHASE_STAMPS: a diagnostic build, never the product library -- wave 0
 // of every workgroup of bb_k2t, bb_k3, bb_k1t and bb_k1_sum keeps
 // s_memrealtime at its phase boundaries and leaves them in a buffer of this
 // build's own (tools/phase_times.py reads it through bsls_phase_read).
-#ifndef BSLS_K1_SUM_EARLY
-#define BSLS_K1_SUM_EARLY 1
-#endif
-#ifndef BSLS_K1_SUM_PAIRS
-#define BSLS_K1_SUM_PAIRS 1
-#endif
-#ifndef BSLS_WT_RPART
-#define BSLS_WT_RPART 1
-#endif
-
 #ifdef BSLS_PHASE_STAMPS
 constexpr int PH_SLOTS = 8, PH_WGS = 4096;
 enum { PH_K2 = 0, PH_K3 = 1, PH_K1 = 2, PH_SUM = 3 };
@@ -386,40 +373,29 @@ __global__ __launch_bounds__(1024) void bb_k1(bsls_bb_problem P, int64_t iter, u
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned prev =
-            __hip_atomic_fetch_add(&tkrb[rb], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        row_last = (prev == (unsigned)G - 1);
-        if (row_last) __hip_atomic_store(&tkrb[rb], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!row_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (!rowblock_last(tkrb, rb, G, &row_last)) return;
     const int64_t r0 = rb * PANEL_WAVES * M.prow;
     const int64_t r1 = (r0 + PANEL_WAVES * M.prow < P.m) ? r0 + PANEL_WAVES * M.prow : P.m;
     const unsigned nrb = (unsigned)((M.npanels + PANEL_WAVES - 1) / PANEL_WAVES);
     k1_finish<ADD, REDUCE>(P, iter, ITER, rb, nrb, r0, r1, G, nullptr, part, ticket, lds);
 }
 
-// BSLS_K1_SPLIT (default 1): a K1 tile launch with several column groups ends
-// once its partials are stored, and bb_k1_sum finishes the rows in a launch of
-// its own -- the kernel boundary replaces the in-kernel hand-off (partials
-// drained, a ticket per row block, the last arriver's loads, a second ticket
-// for ||r||^2: a chain of dependent round trips that took ~half of C3's K1)
-#ifndef BSLS_K1_SPLIT
-#define BSLS_K1_SPLIT 1
-#endif
-
+// A K1 tile launch with several column groups ends once its partials are
+// stored, and bb_k1_sum finishes the rows in a launch of its own -- the kernel
+// boundary replaces an in-kernel hand-off (partials drained, a ticket per row
+// block, the last arriver's loads, a second ticket for ||r||^2: a chain of
+// dependent round trips that took ~half of C3's K1; that finish inside bb_k1t
+// last existed at commit 36c7740).
+//
 // K1's finish as its own launch (rows [r0, r1), one thread per row): r = the G
 // partials in group order (+ target, ADD), ||r||^2 and f by the last block
 // (REDUCE), as k1_finish.
-// W = 2 (BSLS_K1_SUM_PAIRS; the launch: m and r0 even, r1 - r0 >= 2, 16-B
-// aligned arrays): item idx of a thread is the row pair r0 + 2 idx, + 1,
-// loaded and stored as 16 bytes; the single last row of an odd r1 - r0 is
-// the grid's last thread's, after its pairs.  W = 1: an item is a row.  A
-// thread's first item is loaded at a clamped index before the stop test
-// (BSLS_K1_SUM_EARLY: the flag's round trip and the rows' run together;
-// nothing is stored before the test).
+// W = 2 (the launch: m and r0 even, r1 - r0 >= 2, 16-B aligned arrays): item
+// idx of a thread is the row pair r0 + 2 idx, + 1, loaded and stored as 16
+// bytes; the single last row of an odd r1 - r0 is the grid's last thread's,
+// after its pairs.  W = 1: an item is a row.  A thread's first item is loaded
+// at a clamped index before the stop test (the flag's round trip and the
+// rows' run together; nothing is stored before the test).
 template <int W>
 struct K1SumVec {
     typedef double type;
@@ -461,13 +437,12 @@ __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter
             v[c] = (c < G) ? *reinterpret_cast<const vec *>(&P.rpart[c * P.m + row]) : vec{};
         tg = ADD ? *reinterpret_cast<const vec *>(&P.target[row]) : vec{};
     };
-    if (BSLS_K1_SUM_EARLY) load(idx);
+    load(idx);
     if (ITER && stop != 0.0) {
         k1_stopped_rows(P, r0, r1, t0, gs);
         return;
     }
     PH(1);
-    if (!BSLS_K1_SUM_EARLY) load(idx);
     double sq[1] = {0.0};
     unsigned long long mb = 0ull;
     while (idx < ni) {
@@ -526,26 +501,24 @@ __global__ __launch_bounds__(256) void bb_k1_init(bsls_bb_problem P, int64_t r0,
 
 // K1 on a tile image (tiles.hpp): workgroup (rb, g) sums its rows over group
 // g's columns of x in LDS; with one group it finishes the block itself,
-// otherwise it publishes its partials (rpart, sc1) and the last of the block's
-// G workgroups finishes (group order) -- as bb_k1.
-// BSLS_K1T_WGS (variant builds): the workgroups of 1024 threads a CU must
-// hold at once (2: registers capped so two tiles share a CU)
-#ifndef BSLS_K1T_WGS
-#define BSLS_K1T_WGS 1
-#endif
+// otherwise it leaves its partials in rpart for bb_k1_sum (or, ATOM, adds them
+// into r).
+// (__launch_bounds__' second argument: one workgroup of 1024 threads per CU,
+// the whole register file for it.  Two per CU -- registers capped so two
+// tiles share one -- measured slower, profiles/r05_k1_two_tiles_per_cu.log;
+// that variant build last existed at commit 36c7740.)
 // FX (bsls_bb_problem.fx_sums, dealt images, never ATOM): the walk keeps each
 // row's sum in two integer words (tiles.hpp fx_add: order-free), scaled from
 // the caller's bound fx_a1 * x_bound; each row is converted once after the
 // walk, and what follows -- the finish, or the partials and bb_k1_sum -- is the
 // float form's, already ordered.
 template <int MODE, bool ITER, bool ADD, bool REDUCE, bool ATOM = false, bool FX = false>
-__global__ __launch_bounds__(1024, BSLS_K1T_WGS) void bb_k1t(bsls_bb_problem P, int64_t iter, unsigned *tkrb,
-                                               double *part, unsigned *ticket, int64_t rb_base,
-                                               unsigned long long *rmax = nullptr) {
+__global__ __launch_bounds__(1024, 1) void bb_k1t(bsls_bb_problem P, int64_t iter, double *part,
+                                                  unsigned *ticket, int64_t rb_base,
+                                                  unsigned long long *rmax = nullptr) {
     static_assert(!(FX && ATOM), "the fixed-point sums finish through the ordered partials");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double red[32];   // (k1_finish: 2 doubles per wave)
-    __shared__ int row_last;
     const bsls_tiles &T = P.At;
     PH_DECL;
     PH(0);
@@ -553,9 +526,8 @@ __global__ __launch_bounds__(1024, BSLS_K1T_WGS) void bb_k1t(bsls_bb_problem P, 
     tile_map(T, blockIdx.x, gridDim.x / T.ngroups, rb, g);
     rb += rb_base;
     if (ITER && P.scal[BSLS_S_STOP] != 0.0) {
-        // (several groups with the split finish: bb_k1_sum zeroes the rows;
-        // ATOM: bb_k1_init did)
-        if (!ATOM && g == 0 && (T.ngroups == 1 || !BSLS_K1_SPLIT))
+        // (several groups: bb_k1_sum zeroes the rows; ATOM: bb_k1_init did)
+        if (!ATOM && g == 0 && T.ngroups == 1)
             k1_stopped_rows(P, rb * T.H, (rb * T.H + T.H < P.m) ? rb * T.H + T.H : P.m,
                             threadIdx.x, blockDim.x);
         return;
@@ -565,7 +537,7 @@ __global__ __launch_bounds__(1024, BSLS_K1T_WGS) void bb_k1t(bsls_bb_problem P, 
     bool bad = false;
     if constexpr (FX) bad = fx_scale(P.fx_a1 * P.x_bound, fxs, inv);
     // (the clear and its barrier: under the dealt walk's first loads, tiles.hpp
-    // BSLS_WALK_PREFILL)
+    // tile_walk_dealt's `mid`)
     PH(1);
     auto clear = [&]() {
         PH(2);
@@ -609,39 +581,14 @@ __global__ __launch_bounds__(1024, BSLS_K1T_WGS) void bb_k1t(bsls_bb_problem P, 
         }
         return;
     }
-    if (BSLS_K1_SPLIT) {
-        // the partials only; bb_k1_sum (next in the stream) finishes the rows
-        if (BSLS_WT_RPART) {
-            // (a row block's sums fit LDS: the offsets stay far below 2^31)
-            const __amdgpu_buffer_rsrc_t rp = wt_rsrc(P.rpart + g * P.m + r0, r1 - r0);
-            for (int64_t row = r0 + threadIdx.x; row < r1; row += blockDim.x)
-                wt_store_f64(rp, (int)(row - r0) * 8, lds[row - r0]);
-            PH(6);
-            PH_FLUSH(PH_K1);
-            return;
-        }
-        for (int64_t row = r0 + threadIdx.x; row < r1; row += blockDim.x)
-            P.rpart[g * P.m + row] = lds[row - r0];
-        PH(6);
-        PH_FLUSH(PH_K1);
-        return;
-    }
+    // the partials only, through write-through stores; bb_k1_sum (next in the
+    // stream) finishes the rows
+    // (a row block's sums fit LDS: the offsets stay far below 2^31)
+    const __amdgpu_buffer_rsrc_t rp = wt_rsrc(P.rpart + g * P.m + r0, r1 - r0);
     for (int64_t row = r0 + threadIdx.x; row < r1; row += blockDim.x)
-        __hip_atomic_store(&P.rpart[g * P.m + row], lds[row - r0], __ATOMIC_RELAXED,
-                           __HIP_MEMORY_SCOPE_AGENT);
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned prev =
-            __hip_atomic_fetch_add(&tkrb[rb], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        row_last = (prev == (unsigned)G - 1);
-        if (row_last) __hip_atomic_store(&tkrb[rb], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!row_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-    k1_finish<ADD, REDUCE, FX>(P, iter, ITER, rb, (unsigned)T.nrb, r0, r1, G, nullptr, part,
-                               ticket, red, rmax);
+        wt_store_f64(rp, (int)(row - r0) * 8, lds[row - r0]);
+    PH(6);
+    PH_FLUSH(PH_K1);
 }
 
 // K2's epilogue rows per thread per batch (K2E; round 6: 4 -- C3's 3.8 rows
@@ -684,6 +631,36 @@ template <int FUSE>
 __device__ __forceinline__ void k2_stopped_sums(const bsls_bb_problem &P) {
     if (P.shard_role == 2 && blockIdx.x == 0 && threadIdx.x == 0)
         for (int q = 0; q < (FUSE == 2 ? 5 : 4); ++q) P.scal[BSLS_S_SUMDG + q] = 0.0;
+}
+
+// K2's last workgroup, one thread: the reduced sums tot into scal (bb_k2t and
+// bb_k2).  FUSE 1 first records f and runs the stopping test of iteration
+// iter - 1 on tot[4] = ||r||^2; FUSE 2 keeps iteration iter - 1's sums in
+// scal[PSUMDG..PGG] and stores tot[4] as scal[RR].
+template <int FUSE>
+__device__ __forceinline__ void k2_store_sums(const bsls_bb_problem &P, int64_t iter,
+                                              const double (&tot)[FUSE ? 5 : 4]) {
+    if constexpr (FUSE == 1) {
+        bb_record_f(P, iter - 1, tot[4], iter - 1 > 0);
+        // stopped at iter - 1: keep that iteration's sums (what the
+        // unfused schedule leaves in scal); g[iter & 1], written by this
+        // launch, is the other buffer -- the stopping iterate's g is untouched
+        if (P.scal[BSLS_S_STOP] != 0.0) {
+            // (the sums all-reduced after this launch: as k2_stopped_sums)
+            if (P.shard_role == 2)
+                for (int q = 0; q < 4; ++q) P.scal[BSLS_S_SUMDG + q] = 0.0;
+            return;
+        }
+    }
+    if constexpr (FUSE == 2) {
+        double *sc = P.scal;
+        for (int q = 0; q < 4; ++q) sc[BSLS_S_PSUMDG + q] = sc[BSLS_S_SUMDG + q];
+        sc[BSLS_S_RR] = tot[4];
+    }
+    P.scal[BSLS_S_SUMDG] = tot[0];
+    P.scal[BSLS_S_DZDG] = tot[1];
+    P.scal[BSLS_S_DGDG] = tot[2];
+    P.scal[BSLS_S_GG] = tot[3];
 }
 
 // gsel >= 0 (bsls_bb_k2_part): only column group gsel, one workgroup per row
@@ -763,7 +740,7 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
         }
     }
     // (the clear and its barrier: under the dealt walk's first loads, tiles.hpp
-    // BSLS_WALK_PREFILL)
+    // tile_walk_dealt's `mid`)
     auto clear = [&]() {
         PH(2);
         for (int i = threadIdx.x; i < HR; i += blockDim.x) {
@@ -830,17 +807,8 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
             __hip_atomic_store(&wp[i], rows[i], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
-        if (threadIdx.x == 0) {
-            const unsigned prev =
-                __hip_atomic_fetch_add(&tk2rb[rb], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            row_last = (prev == (unsigned)G - 1);
-            if (row_last)
-                __hip_atomic_store(&tk2rb[rb], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        }
-        __syncthreads();
-        fin = row_last;
+        fin = rowblock_last(tk2rb, rb, G, &row_last);
         if (fin) {
-            __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
             for (int64_t i = threadIdx.x; i < nloc; i += blockDim.x) {
                 double o = 0.0;
                 for (int64_t c = 0; c < G; ++c)
@@ -928,29 +896,7 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
     const bool last = (G == 1) ? last_block_sum<NS>(sums, part, ticket, tot, red)
                                : last_of_sum<NS>(sums, part, (unsigned)rb, (unsigned)T.nrb, ticket,
                                                  tot, red);
-    if (last && threadIdx.x == 0) {
-        if constexpr (FUSE == 1) {
-            bb_record_f(P, iter - 1, tot[4], iter - 1 > 0);
-            // stopped at iter - 1: keep that iteration's sums (what the
-            // unfused schedule leaves in scal); g[iter & 1], written above,
-            // is the other buffer -- the stopping iterate's g is untouched
-            if (P.scal[BSLS_S_STOP] != 0.0) {
-                // (the sums all-reduced after this launch: as k2_stopped_sums)
-                if (P.shard_role == 2)
-                    for (int q = 0; q < 4; ++q) P.scal[BSLS_S_SUMDG + q] = 0.0;
-                return;
-            }
-        }
-        if constexpr (FUSE == 2) {
-            double *sc = P.scal;
-            for (int q = 0; q < 4; ++q) sc[BSLS_S_PSUMDG + q] = sc[BSLS_S_SUMDG + q];
-            sc[BSLS_S_RR] = tot[4];
-        }
-        P.scal[BSLS_S_SUMDG] = tot[0];
-        P.scal[BSLS_S_DZDG] = tot[1];
-        P.scal[BSLS_S_DGDG] = tot[2];
-        P.scal[BSLS_S_GG] = tot[3];
-    }
+    if (last && threadIdx.x == 0) k2_store_sums<FUSE>(P, iter, tot);
     PH(7);
     PH_FLUSH(PH_K2);
 }
@@ -1101,26 +1047,8 @@ __global__ __launch_bounds__(1024) void bb_k2(bsls_bb_problem P, const double *_
     }
     block_sum<NS>(sums, lds);
     double tot[NS];
-    if (last_block_sum<NS>(sums, part, ticket, tot, lds) && threadIdx.x == 0) {
-        if constexpr (FUSE == 1) {
-            bb_record_f(P, iter - 1, tot[4], iter - 1 > 0);
-            if (P.scal[BSLS_S_STOP] != 0.0) {
-                // (the sums all-reduced after this launch: as k2_stopped_sums)
-                if (P.shard_role == 2)
-                    for (int q = 0; q < 4; ++q) P.scal[BSLS_S_SUMDG + q] = 0.0;
-                return;
-            }   // as bb_k2t
-        }
-        if constexpr (FUSE == 2) {
-            double *sc = P.scal;
-            for (int q = 0; q < 4; ++q) sc[BSLS_S_PSUMDG + q] = sc[BSLS_S_SUMDG + q];
-            sc[BSLS_S_RR] = tot[4];
-        }
-        P.scal[BSLS_S_SUMDG] = tot[0];
-        P.scal[BSLS_S_DZDG] = tot[1];
-        P.scal[BSLS_S_DGDG] = tot[2];
-        P.scal[BSLS_S_GG] = tot[3];
-    }
+    if (last_block_sum<NS>(sums, part, ticket, tot, lds) && threadIdx.x == 0)
+        k2_store_sums<FUSE>(P, iter, tot);
 }
 
 // x entry i of N z; for a scaled incidence K1 gathers colv[i] * x_i instead,
@@ -1164,9 +1092,6 @@ __device__ __forceinline__ bool bb_step_t(const bsls_bb_problem &P, int64_t iter
 
 #ifndef BSLS_K3_SGPRS
 #define BSLS_K3_SGPRS 80
-#endif
-#ifndef BSLS_DZ_PLAIN
-#define BSLS_DZ_PLAIN 0   // 1: dz through an ordinary store (A/B variant)
 #endif
 
 // Each wave takes K3_PPW packs (w, w + W, ...; W = waves in the grid) and
@@ -1287,11 +1212,10 @@ void bb_k3(bsls_bb_problem P, int64_t iter,
     PH(2);
 #endif
     if (BSLS_K3_KO != 1) {
-        // warm start: the last run partition of each pack, tested first
-        // (pava_warm); a pack that passes needs no reference pass
-        // (BSLS_K3_REPAIR, the default: a partition that fails is repaired
-        // -- its unsplittable runs kept pooled -- and the reference passes
-        // continue from it, pava_warm_repair)
+        // warm start: the last run partition of each pack, tested first; a
+        // pack that passes needs no reference pass, and a partition that
+        // fails is repaired -- its unsplittable runs kept pooled -- and the
+        // reference passes continue from it (pava_warm_repair)
         bool need[K3_PPW], store[K3_PPW];
         uint64_t Hn[K3_PPW];
 #pragma unroll
@@ -1299,13 +1223,9 @@ void bb_k3(bsls_bb_problem P, int64_t iter,
             need[q] = L[q] > 0 && L[q] <= WAVE;
             store[q] = need[q];
             if (hd && need[q] && (H[q] & B[q]) == B[q] && (H[q] & ~mask_lt(L[q])) == 0ull) {
-#if BSLS_K3_REPAIR
                 store[q] = pava_warm_repair(yv[q], L[q], B[q], H[q], pv_y[wv], pv_p[wv],
                                             pv_c[wv], &Hn[q]);
                 need[q] = false;
-#else
-                need[q] = store[q] = !pava_warm(yv[q], L[q], B[q], H[q]);
-#endif
             }
         }
         if (MERGE && K3_PPW == 2 && need[0] && need[K3_PPW - 1]) {
@@ -1343,11 +1263,7 @@ void bb_k3(bsls_bb_problem P, int64_t iter,
                 P.x + z0[q] + b0[q], 0, (L[q] + nb) * 8, 0x00020000);
             if (act) {
                 wt_store_f64(rz, l * 8, v);
-#if BSLS_DZ_PLAIN
-                dzo[z0[q] + l] = v - zv[q];
-#else
                 wt_store_f64(rd, l * 8, v - zv[q]);   // next K2's z - z_prev
-#endif
                 const double d = v - (bstart ? 0.0 : vprev);
                 const int xo = (l + bl) * 8;
                 wt_store_f64(rx, xo, P.colv ? cv[q] * d : d);
@@ -1500,6 +1416,26 @@ static bool k1_init_folded(const bsls_bb_problem &P) {
     return P.At.ent && P.At.ngroups > 1 && k1_atomic(P, false);
 }
 
+// bb_k1_sum behind a several-group bb_k1t over row blocks [rb0, rb1): rows in
+// 16-B pairs (W = 2) where every pair is aligned in rpart, target and r
+template <bool ITER, bool ADD, bool REDUCE, bool FX>
+static void launch_k1_sum(const bsls_bb_problem &P, int64_t iter, const BBWork &w, hipStream_t st,
+                          int64_t rb0, int64_t rb1) {
+    const int64_t r0 = rb0 * P.At.H, r1 = (rb1 * P.At.H < P.m) ? rb1 * P.At.H : P.m;
+    constexpr int K1_SUM_GRID = 1024;
+    const bool pairs = !(P.m & 1) && !(r0 & 1) && r1 - r0 >= 2 &&
+                       !(((uintptr_t)P.rpart | (uintptr_t)P.target | (uintptr_t)P.r) & 15);
+    const int gk = grid_for(pairs ? (r1 - r0) / 2 : r1 - r0, 256);
+    const int grid = (REDUCE && gk > K1_SUM_GRID) ? K1_SUM_GRID : gk;
+    unsigned long long *rmax = FX ? w.rmax : nullptr;
+    if (pairs)
+        bb_k1_sum<ITER, ADD, REDUCE, 2, FX><<<grid, 256, 0, st>>>(P, iter, P.At.ngroups, r0, r1,
+                                                                  w.pf, w.tkf, rmax);
+    else
+        bb_k1_sum<ITER, ADD, REDUCE, 1, FX><<<grid, 256, 0, st>>>(P, iter, P.At.ngroups, r0, r1,
+                                                                  w.pf, w.tkf, rmax);
+}
+
 // K1 with fixed-point row sums (bsls_bb_problem.fx_sums): bb_k1t's FX form and,
 // with several groups, bb_k1_sum's -- the launches of the float form
 template <int MODE, bool REDUCE, bool ITER>
@@ -1509,23 +1445,8 @@ static void launch_k1t_fx(const bsls_bb_problem &P, int64_t iter, const BBWork &
     bb_k1t<MODE, ITER, true, REDUCE, false, true><<<(int)((rb1 - rb0) * P.At.ngroups),
                                                     BSLS_TILE_THREADS,
                                                     tile_lds_doubles(P.At, true) * 8, st>>>(
-        P, iter, w.tkrb, w.p1, w.tk1, rb0, w.rmax);
-    if (!(BSLS_K1_SPLIT && P.At.ngroups > 1)) return;
-    const int64_t r0 = rb0 * P.At.H, r1 = (rb1 * P.At.H < P.m) ? rb1 * P.At.H : P.m;
-    constexpr int K1_SUM_GRID = 1024;
-    const bool pairs = BSLS_K1_SUM_PAIRS && !(P.m & 1) && !(r0 & 1) && r1 - r0 >= 2 &&
-                       !(((uintptr_t)P.rpart | (uintptr_t)P.target | (uintptr_t)P.r) & 15);
-    if (pairs) {
-        const int gk = grid_for((r1 - r0) / 2, 256);
-        bb_k1_sum<ITER, true, REDUCE, 2, true><<<(REDUCE && gk > K1_SUM_GRID) ? K1_SUM_GRID : gk,
-                                                 256, 0, st>>>(P, iter, P.At.ngroups, r0, r1, w.pf,
-                                                               w.tkf, w.rmax);
-        return;
-    }
-    const int gk = grid_for(r1 - r0, 256);
-    bb_k1_sum<ITER, true, REDUCE, 1, true><<<(REDUCE && gk > K1_SUM_GRID) ? K1_SUM_GRID : gk, 256,
-                                             0, st>>>(P, iter, P.At.ngroups, r0, r1, w.pf, w.tkf,
-                                                      w.rmax);
+        P, iter, w.p1, w.tk1, rb0, w.rmax);
+    if (P.At.ngroups > 1) launch_k1_sum<ITER, true, REDUCE, true>(P, iter, w, st, rb0, rb1);
 }
 
 template <int MODE, bool ADD, bool REDUCE, bool ITER>
@@ -1542,7 +1463,7 @@ static void launch_k1t_mode(const bsls_bb_problem &P, int64_t iter, const BBWork
         allow_lds(bb_k1t<MODE, ITER, ADD, false, true>);
         bb_k1t<MODE, ITER, ADD, false, true><<<(int)((rb1 - rb0) * P.At.ngroups),
                                                BSLS_TILE_THREADS, tile_lds_doubles(P.At, false) * 8,
-                                               st>>>(P, iter, w.tkrb, w.p1, w.tk1, rb0);
+                                               st>>>(P, iter, w.p1, w.tk1, rb0);
         if (REDUCE)
             bb_r_finish<<<(grid_for(P.m, 256) < R_FINISH_GRID ? grid_for(P.m, 256) : R_FINISH_GRID),
                           256, 0, st>>>(P, iter, w.pf, w.tkf, 0);
@@ -1560,24 +1481,9 @@ static void launch_k1t_mode(const bsls_bb_problem &P, int64_t iter, const BBWork
     }
     allow_lds(bb_k1t<MODE, ITER, ADD, REDUCE>);
     bb_k1t<MODE, ITER, ADD, REDUCE><<<(int)((rb1 - rb0) * P.At.ngroups), BSLS_TILE_THREADS,
-                                      tile_lds_doubles(P.At, false) * 8, st>>>(P, iter, w.tkrb,
-                                                                                w.p1, w.tk1, rb0);
-    if (BSLS_K1_SPLIT && P.At.ngroups > 1) {
-        const int64_t r0 = rb0 * P.At.H, r1 = (rb1 * P.At.H < P.m) ? rb1 * P.At.H : P.m;
-        constexpr int K1_SUM_GRID = 1024;
-        // rows in 16-B pairs where every pair is aligned in rpart, target and r
-        const bool pairs = BSLS_K1_SUM_PAIRS && !(P.m & 1) && !(r0 & 1) && r1 - r0 >= 2 &&
-                           !(((uintptr_t)P.rpart | (uintptr_t)P.target | (uintptr_t)P.r) & 15);
-        if (pairs) {
-            const int gk = grid_for((r1 - r0) / 2, 256);
-            bb_k1_sum<ITER, ADD, REDUCE, 2><<<(REDUCE && gk > K1_SUM_GRID) ? K1_SUM_GRID : gk, 256,
-                                              0, st>>>(P, iter, P.At.ngroups, r0, r1, w.pf, w.tkf);
-            return;
-        }
-        const int gk = grid_for(r1 - r0, 256);
-        bb_k1_sum<ITER, ADD, REDUCE><<<(REDUCE && gk > K1_SUM_GRID) ? K1_SUM_GRID : gk, 256, 0, st>>>(
-            P, iter, P.At.ngroups, r0, r1, w.pf, w.tkf);
-    }
+                                      tile_lds_doubles(P.At, false) * 8, st>>>(P, iter, w.p1,
+                                                                                w.tk1, rb0);
+    if (P.At.ngroups > 1) launch_k1_sum<ITER, ADD, REDUCE, false>(P, iter, w, st, rb0, rb1);
 }
 
 template <bool ADD, bool REDUCE, bool ITER>
@@ -1592,6 +1498,24 @@ static void launch_k1(const bsls_bb_problem &P, int64_t iter, const BBWork &w, h
     } else {
         launch_k1_mode<1, ADD, REDUCE, ITER>(P, iter, w, st, rb0, rb1);
     }
+}
+
+// A column shard's partial residual (stages 1 / 14, bsls_bb_residual_rows,
+// bsls_bb_k1_rows): the shard_role 1 rank adds target, the stop test runs
+// inside an iteration only, and ||r||^2 waits for the all-reduce of r
+static void launch_k1_partial(const bsls_bb_problem &P, int64_t iter, const BBWork &w,
+                              hipStream_t st, int64_t rb0 = 0, int64_t rb1 = -1,
+                              bool skip_init = false) {
+    const bool add = P.shard_role == 1;
+    if (add && iter > 0) launch_k1<true, false, true>(P, iter, w, st, rb0, rb1, skip_init);
+    else if (add) launch_k1<true, false, false>(P, iter, w, st, rb0, rb1, skip_init);
+    else if (iter > 0) launch_k1<false, false, true>(P, iter, w, st, rb0, rb1, skip_init);
+    else launch_k1<false, false, false>(P, iter, w, st, rb0, rb1, skip_init);
+}
+
+// fx_sums: max|r| back to 0 ahead of a K1 finish that no K3 has cleared it for
+static hipError_t clear_rmax(const bsls_bb_problem &P, const BBWork &w, hipStream_t st) {
+    return P.fx_sums ? hipMemsetAsync(w.rmax, 0, RMAX_SLOTS * 8, st) : hipSuccess;
 }
 
 // (dz: the vector the ITER sums dot with delta_g -- the workspace's z - z_prev
@@ -1764,400 +1688,13 @@ static int check_problem_float(const bsls_bb_problem *p) {
     return p->fx_sums ? BSLS_E_ARG : BSLS_OK;
 }
 
-// ---- LBFGS.solve's weak Wolfe line search on the device -------------------------
-// (python/LBFGS.py:9-53; include/bsls_hip.h bsls_lbfgs_ls_*).  One trial =
-//   K3 on S1:  pt = clip01(PAVA(x - (-t) d)) = proj(x + t d) (the reference's
-//              roundings: (-t) d = -(t d)), x_engine = colv N pt
-//   K1 on S1:  r = A x + target, S1[FX] = f(pt)
-//   armijo:    f(pt) >= fx + c1 t slope -> beta = t, t = (alpha + beta) / 2;
-//              else open S2 for the curvature test
-//   K2 on S2:  g(pt) = N'A'r -> gpt; the sums with g_prev = 0 and dz = d give
-//              S2[DZDG] = d . g(pt)
-//   curvature: d . g(pt) < c2 slope -> alpha = t, t = 2 alpha or (alpha +
-//              beta) / 2; else accepted
-// then the reference's two exits (|alpha - beta| <= 1e-14, ||t d|| <= 1e-8,
-// the norm as |t| ||d||).  Every kernel of a trial is gated by the state, so
-// the host enqueues trials in chunks and reads the state once per chunk.
-// st[]: BSLS_LS_* slots.
-__device__ __forceinline__ void ls_stop(double *st, double *S1, double *S2, double why) {
-    st[BSLS_LS_STOP] = why;
-    S1[BSLS_S_STOP] = 1.0;
-    S2[BSLS_S_STOP] = 1.0;
-}
-
-// the exits after a new t (LBFGS.py:45-49), else the next trial's K3 step
-__device__ __forceinline__ void ls_next(double *st, double *S1, double *S2, double tn) {
-    st[BSLS_LS_T] = tn;
-    if (fabs(st[BSLS_LS_LO] - st[BSLS_LS_HI]) <= 1e-14) ls_stop(st, S1, S2, BSLS_LS_BRACKET);
-    else if (fabs(tn) * st[BSLS_LS_DNORM] <= 1e-8) ls_stop(st, S1, S2, BSLS_LS_SMALL);
-    else S1[BSLS_S_DZDG] = -tn;
-}
-
-__global__ __launch_bounds__(256) void ls_begin_kernel(const double *__restrict__ d,
-                                                       const double *__restrict__ gx, int64_t nz,
-                                                       const double *fx, double *st,
-                                                       double *S1, double *S2, double *part,
-                                                       unsigned *tickets) {
-    __shared__ double red[2 * 4];
-    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    double v[2] = {0.0, 0.0};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nz; i += gs) {
-        const double di = d[i];
-        v[0] += di * gx[i];
-        v[1] += di * di;
-    }
-    block_sum<2>(v, red);
-    double tot[2];
-    if (last_block_sum<2>(v, part, tickets, tot, red) && threadIdx.x == 0) {
-        const double f0 = *fx;    // (fx may point into st: the last search's st[FT])
-        for (int k = 0; k < BSLS_LS_COUNT; ++k) st[k] = 0.0;
-        for (int k = 0; k < BSLS_S_COUNT; ++k) S1[k] = S2[k] = 0.0;
-        st[BSLS_LS_T] = 1.0;
-        st[BSLS_LS_HI] = INFINITY;
-        st[BSLS_LS_SLOPE] = tot[0];
-        st[BSLS_LS_DNORM] = sqrt(tot[1]);
-        st[BSLS_LS_FX] = f0;
-        S1[BSLS_S_SUMDG] = 1.0;      // K3's t = S1[DZDG] / S1[DGDG] = -t
-        S1[BSLS_S_DZDG] = -1.0;
-        S1[BSLS_S_DGDG] = 1.0;
-        S2[BSLS_S_STOP] = 1.0;
-    }
-}
-
-__global__ void ls_armijo_kernel(double *st, double *S1, double *S2, double c1) {
-    if (threadIdx.x != 0 || st[BSLS_LS_STOP] != 0.0) return;
-    const double t = st[BSLS_LS_T], ft = S1[BSLS_S_FX];
-    st[BSLS_LS_NTRIAL] += 1.0;
-    st[BSLS_LS_TLAST] = t;
-    st[BSLS_LS_FT] = ft;
-    if (ft >= st[BSLS_LS_FX] + c1 * t * st[BSLS_LS_SLOPE]) {   // Armijo violated (LBFGS.py:26)
-        st[BSLS_LS_HI] = t;
-        S2[BSLS_S_STOP] = 1.0;
-        ls_next(st, S1, S2, 0.5 * (st[BSLS_LS_LO] + t));
-    } else {
-        S2[BSLS_S_STOP] = 0.0;     // the curvature test needs g(pt)
-    }
-}
-
-__global__ void ls_curv_kernel(double *st, double *S1, double *S2, double c2) {
-    if (threadIdx.x != 0 || st[BSLS_LS_STOP] != 0.0 || S2[BSLS_S_STOP] != 0.0) return;
-    const double t = st[BSLS_LS_T];
-    S2[BSLS_S_STOP] = 1.0;
-    st[BSLS_LS_DGT] = S2[BSLS_S_DZDG];
-    if (S2[BSLS_S_DZDG] < c2 * st[BSLS_LS_SLOPE]) {            // curvature violated (:33)
-        st[BSLS_LS_LO] = t;
-        const double hi = st[BSLS_LS_HI];
-        ls_next(st, S1, S2, (hi == INFINITY) ? 2 * t : 0.5 * (t + hi));
-    } else {
-        ls_stop(st, S1, S2, BSLS_LS_ACCEPTED);                  // both conditions pass (:39)
-    }
-}
-
-// after an accepted search: y = g(pt) - gx, s = t d (LBFGS.py:100-106, the
-// same elementwise roundings), y.s and g(pt).g(pt); gated on the state
-__global__ __launch_bounds__(256) void ls_finish_kernel(const double *__restrict__ d,
-                                                        const double *__restrict__ gx,
-                                                        const double *__restrict__ gpt, int64_t nz,
-                                                        double *st, double *y_out, double *s_out,
-                                                        double *part, unsigned *tickets) {
-    __shared__ double red[2 * 4];
-    if (st[BSLS_LS_STOP] != (double)BSLS_LS_ACCEPTED || st[BSLS_LS_DONE] != 0.0) return;
-    const double t = st[BSLS_LS_T];
-    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    double v[2] = {0.0, 0.0};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < nz; i += gs) {
-        const double gi = gpt[i];
-        const double y = gi - gx[i], s = t * d[i];
-        if (y_out) y_out[i] = y;
-        if (s_out) s_out[i] = s;
-        v[0] += y * s;
-        v[1] += gi * gi;
-    }
-    block_sum<2>(v, red);
-    double tot[2];
-    if (last_block_sum<2>(v, part, tickets, tot, red) && threadIdx.x == 0) {
-        st[BSLS_LS_YS] = tot[0];
-        st[BSLS_LS_GG] = tot[1];
-        st[BSLS_LS_DONE] = 1.0;
-    }
-}
-
-// ---- DORE on the fused images (include/bsls_hip.h bsls_dore_iterate) --------
-// Vector steps of python/DORE.py:31-80 with the reference's elementwise
-// roundings; dot products as fixed-order block sums; every branch decided by
-// the last block of a reduction and read by the kernels after it.
-
-// Ax = linop(x), err = b - Ax; norm_change = ||x - x_prev||^2 (la.norm(.)**2:
-// the square of the rooted sum) and the break test.  Ax is scale * r of this
-// launch's K1 at iteration 0 (axs == nullptr); after that x is the previous
-// iteration's x_select, whose linop the previous iteration already formed
-// (axs: its Ax, = scale * r of K1 on the same x -- the reference recomputes
-// it at DORE.py:33, here it is reused, one K1 and one z2x fewer per iteration)
-__global__ __launch_bounds__(256) void dore_top(bsls_bb_problem P, bsls_dore_state D, int64_t it,
-                                                const double *__restrict__ x,
-                                                const double *__restrict__ xp,
-                                                const double *__restrict__ axs) {
-    __shared__ double red[4];
-    if (D.S[BSLS_S_STOP] != 0.0) return;
-    if (blockIdx.x == 0 && threadIdx.x == 0) {
-        D.S2[BSLS_S_STOP] = 1.0;     // the extrapolated path stays off unless dore_mid opens it
-        D.dsc[BSLS_DORE_SEL] = 0.0;
-    }
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = i0; i < P.m; i += gs) {
-        const double ax = axs ? axs[i] : P.r[i] * D.scale;
-        D.err[i] = D.b[i] - ax;
-    }
-    double v[1] = {0.0};
-    for (int64_t i = i0; i < P.nz; i += gs) {
-        const double t = x[i] - xp[i];
-        v[0] += t * t;
-    }
-    block_sum<1>(v, red);
-    double tot[1];
-    if (last_block_sum<1>(v, D.part, D.tickets, tot, red) && threadIdx.x == 0) {
-        const double nr = sqrt(tot[0]);
-        const double nc = nr * nr;
-        D.dsc[BSLS_DORE_NC] = nc;
-        if (it > 0 && nc <= D.eps) {
-            D.S[BSLS_S_STOP] = 1.0;
-            D.dsc[BSLS_DORE_STOPIT] = (double)it;
-        }
-    }
-}
-
-// Ax = linop(x_new) -> axo; err; ||err||^2; i > 2: dAx = Ax - Ax_prev, dp, dAx.err
-__global__ __launch_bounds__(256) void dore_mid(bsls_bb_problem P, bsls_dore_state D, int64_t it,
-                                                double *__restrict__ axo,
-                                                const double *__restrict__ axp) {
-    __shared__ double red[3 * 4];
-    if (D.S[BSLS_S_STOP] != 0.0) return;
-    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    double v[3] = {0.0, 0.0, 0.0};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P.m; i += gs) {
-        const double ax = P.r[i] * D.scale;
-        axo[i] = ax;
-        const double e = D.b[i] - ax;
-        D.err[i] = e;
-        v[0] += e * e;
-        if (it > 2) {
-            const double d = ax - axp[i];
-            v[1] += d * d;
-            v[2] += d * e;
-        }
-    }
-    block_sum<3>(v, red);
-    double tot[3];
-    if (last_block_sum<3>(v, D.part, D.tickets, tot, red) && threadIdx.x == 0) {
-        D.dsc[BSLS_DORE_EE] = tot[0];
-        const bool ext = it > 2 && tot[1] > 0;
-        if (ext) D.dsc[BSLS_DORE_A1] = tot[2] / tot[1];
-        D.S2[BSLS_S_STOP] = ext ? 0.0 : 1.0;
-    }
-}
-
-// first extrapolation: Ax_1 = (1 + a1) Ax - a1 Ax_prev, err_1 = b - Ax_1,
-// dAx = Ax_1 - Ax_prev_prev (dp, dAx.err_1); x_1 = x_new + a1 (x_new - x) and
-// x_1 - x_prev for the second; a2 and the K3 step t = -a2 into S2
-__global__ __launch_bounds__(256) void dore_ext(bsls_bb_problem P, bsls_dore_state D,
-                                                const double *__restrict__ ax,
-                                                const double *__restrict__ axp,
-                                                const double *__restrict__ axpp,
-                                                const double *__restrict__ x,
-                                                const double *__restrict__ xp,
-                                                const double *__restrict__ xn) {
-    __shared__ double red[2 * 4];
-    if (D.S[BSLS_S_STOP] != 0.0 || D.S2[BSLS_S_STOP] != 0.0) return;
-    const double a1 = D.dsc[BSLS_DORE_A1];
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    double v[2] = {0.0, 0.0};
-    for (int64_t i = i0; i < P.m; i += gs) {
-        const double ax1 = (1 + a1) * ax[i] - a1 * axp[i];
-        const double e1 = D.b[i] - ax1;
-        const double d = ax1 - axpp[i];
-        v[0] += d * d;
-        v[1] += d * e1;
-    }
-    for (int64_t i = i0; i < P.nz; i += gs) {
-        const double x1 = xn[i] + a1 * (xn[i] - x[i]);
-        D.X1[i] = x1;
-        D.D[i] = x1 - xp[i];
-    }
-    block_sum<2>(v, red);
-    double tot[2];
-    if (last_block_sum<2>(v, D.part, D.tickets, tot, red) && threadIdx.x == 0) {
-        if (tot[0] > 0) {
-            const double a2 = tot[1] / tot[0];
-            D.dsc[BSLS_DORE_A2] = a2;
-            D.S2[BSLS_S_SUMDG] = 1.0;
-            D.S2[BSLS_S_DZDG] = -a2;    // K3: x_1 - (-a2) (x_1 - x_prev) = x_1 + a2 (...)
-            D.S2[BSLS_S_DGDG] = 1.0;
-        } else {
-            D.S2[BSLS_S_STOP] = 1.0;
-        }
-    }
-}
-
-// Ax_2 = linop(x_2), err_2; keep x_2 when ||err_2||^2 / ||err||^2 < 1
-__global__ __launch_bounds__(256) void dore_sel(bsls_bb_problem P, bsls_dore_state D) {
-    __shared__ double red[4];
-    if (D.S[BSLS_S_STOP] != 0.0 || D.S2[BSLS_S_STOP] != 0.0) return;
-    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    double v[1] = {0.0};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P.m; i += gs) {
-        const double ax2 = P.r[i] * D.scale;
-        D.AX2[i] = ax2;
-        const double e = D.b[i] - ax2;
-        v[0] += e * e;
-    }
-    block_sum<1>(v, red);
-    double tot[1];
-    if (last_block_sum<1>(v, D.part, D.tickets, tot, red) && threadIdx.x == 0)
-        D.dsc[BSLS_DORE_SEL] = (tot[0] / D.dsc[BSLS_DORE_EE] < 1) ? 1.0 : 0.0;
-}
-
-// x_select = x_2, Ax = Ax_2 when selected
-__global__ __launch_bounds__(256) void dore_copy(bsls_bb_problem P, bsls_dore_state D,
-                                                 double *__restrict__ xn,
-                                                 double *__restrict__ axo) {
-    if (D.S[BSLS_S_STOP] != 0.0 || D.S2[BSLS_S_STOP] != 0.0 || D.dsc[BSLS_DORE_SEL] == 0.0)
-        return;
-    const int64_t i0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    const int64_t gs = (int64_t)gridDim.x * blockDim.x;
-    for (int64_t i = i0; i < P.nz; i += gs) xn[i] = D.X2[i];
-    for (int64_t i = i0; i < P.m; i += gs) axo[i] = D.AX2[i];
-}
-
 }  // namespace bsls
 
 using namespace bsls;
 
-extern "C" size_t bsls_dore_work_size(int64_t nz, int64_t m) {
-    const int64_t n = (nz > m ? nz : m);
-    return (size_t)((n + 255) / 256 + 1) * 3 * sizeof(double);
-}
-
-extern "C" int bsls_dore_iterate(const bsls_bb_problem *p, const bsls_dore_state *d,
-                                 int64_t first_iter, int64_t count, void *stream) {
-    const int rc = check_problem_float(p);
-    if (rc != BSLS_OK) return rc;
-    if (!d || first_iter < 0 || count < 0 || !d->X1 || !d->D || !d->X2 || !d->AX2 || !d->err ||
-        !d->b || !d->S || !d->S2 || !d->dsc || !d->part || !d->tickets)
-        return BSLS_E_ARG;
-    for (int k = 0; k < 3; ++k)
-        if (!d->X[k] || !d->AX[k]) return BSLS_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const BBWork w = bb_layout(*p);
-    bsls_bb_problem PS = *p, P2 = *p, PE = *p;
-    PS.scal = d->S;
-    PE.scal = d->S;
-    PE.r = d->err;                       // K2 reads err as its r
-    P2.scal = d->S2;
-    const bsls_dore_state D = *d;
-    const int64_t big = (p->nz > p->m ? p->nz : p->m);
-    // grid-stride elementwise steps: a fixed grid of at most DORE_GRID blocks
-    // (two per CU), each thread summing its elements in stride order, so the
-    // reductions' fan-in is DORE_GRID arrivals instead of one per 256
-    // elements (C3: 3.7k workgroups made dore_top / dore_ext ~17 us for
-    // ~18 / ~40 MB)
-    constexpr int DORE_GRID = 512;
-    const int gb0 = grid_for(big, 256), gm0 = grid_for(p->m, 256);
-    const int gb = gb0 < DORE_GRID ? gb0 : DORE_GRID, gm = gm0 < DORE_GRID ? gm0 : DORE_GRID;
-    for (int64_t i = first_iter; i < first_iter + count; ++i) {
-        double *x = d->X[i % 3], *xp = d->X[(i + 2) % 3], *xn = d->X[(i + 1) % 3];
-        double *axo = d->AX[i % 3], *axp = d->AX[(i + 2) % 3], *axpp = d->AX[(i + 1) % 3];
-        // Ax = linop(x), err, norm_change (DORE.py:31-37); from iteration 1 on
-        // x is the last x_select and Ax its linop, kept in axp (dore_top)
-        static const bool recompute = [] {   // BSLS_DORE_RECOMPUTE=1: the reference's K1 (A/B)
-            const char *e = getenv("BSLS_DORE_RECOMPUTE");
-            return e && e[0] == '1';
-        }();
-        const bool top_k1 = i == 0 || recompute;
-        if (top_k1) {
-            bb_z2x<<<grid_for(p->n, 256), 256, 0, st>>>(PS, x);
-            launch_k1<false, false, true>(PS, i, w, st);
-        }
-        dore_top<<<gb, 256, 0, st>>>(PS, D, i, x, xp, top_k1 ? nullptr : axp);
-        // x_new = proj(x + linop_T(err)) (DORE.py:38-40; K3 with t = -scale)
-        launch_k2<false>(PE, nullptr, p->g[0], w, st);
-        launch_k3(PS, i, x, p->g[0], xn, w, st);
-        // Ax = linop(x_new), err (DORE.py:41-42) and the first extrapolation
-        launch_k1<false, false, true>(PS, i, w, st);
-        dore_mid<<<gm, 256, 0, st>>>(PS, D, i, axo, axp);
-        dore_ext<<<gb, 256, 0, st>>>(PS, D, axo, axp, axpp, x, xp, xn);
-        // x_2 = proj(x_1 + a2 (x_1 - x_prev)), Ax_2 = linop(x_2), selection (DORE.py:55-69)
-        launch_k3(P2, i, d->X1, d->D, d->X2, w, st, 0, 1);
-        launch_k1<false, false, true>(P2, i, w, st);
-        dore_sel<<<gm, 256, 0, st>>>(P2, D);
-        dore_copy<<<gb, 256, 0, st>>>(P2, D, xn, axo);
-        BSLS_LAUNCH_CHECK();
-    }
-    return BSLS_OK;
-}
-
-extern "C" size_t bsls_lbfgs_ls_work_size(int64_t nz) {
-    return (size_t)(((nz > 0 ? nz : 1) + 255) / 256 + 1) * 2 * sizeof(double);
-}
-
-static int check_ls(const bsls_ls_state *s) {
-    if (!s || !s->x || !s->d || !s->gx || !s->pt || !s->gpt || !s->zero || !s->fx || !s->st ||
-        !s->S1 || !s->S2 || !s->part || !s->tickets)
-        return BSLS_E_ARG;
-    return BSLS_OK;
-}
-
-extern "C" int bsls_lbfgs_ls_begin(const bsls_bb_problem *p, const bsls_ls_state *s, void *stream) {
-    int rc = check_problem_float(p);
-    if (rc != BSLS_OK || (rc = check_ls(s)) != BSLS_OK) return rc;
-    constexpr int LS_GRID = 512;
-    const int g = grid_for(p->nz, 256);
-    ls_begin_kernel<<<g < LS_GRID ? g : LS_GRID, 256, 0, (hipStream_t)stream>>>(
-        s->d, s->gx, p->nz, s->fx, s->st, s->S1, s->S2, s->part, s->tickets);
-    BSLS_LAUNCH_CHECK();
-    return BSLS_OK;
-}
-
-extern "C" int bsls_lbfgs_ls_trials(const bsls_bb_problem *p, const bsls_ls_state *s,
-                                    int64_t count, void *stream) {
-    int rc = check_problem_float(p);
-    if (rc != BSLS_OK || (rc = check_ls(s)) != BSLS_OK) return rc;
-    if (count < 0) return BSLS_E_ARG;
-    hipStream_t st = (hipStream_t)stream;
-    const BBWork w = bb_layout(*p);
-    // the trial's problems: S1 gates K3 / K1 (and takes f), S2 gates K2; no
-    // stopping rule of their own (max_iter unreachable, no early exits)
-    bsls_bb_problem P1 = *p, P2 = *p;
-    P1.scal = s->S1;
-    P2.scal = s->S2;
-    P1.max_iter = P2.max_iter = INT64_MAX;
-    P1.early_exit = P2.early_exit = 0;
-    for (int64_t k = 0; k < count; ++k) {
-        launch_k3(P1, 1, s->x, s->d, s->pt, w, st, 0, 1);
-        BSLS_LAUNCH_CHECK();
-        launch_k1<true, true, true>(P1, 1, w, st);
-        BSLS_LAUNCH_CHECK();
-        ls_armijo_kernel<<<1, 64, 0, st>>>(s->st, s->S1, s->S2, s->c1);
-        launch_k2<true>(P2, s->zero, s->gpt, w, st, 1, s->d);
-        BSLS_LAUNCH_CHECK();
-        ls_curv_kernel<<<1, 64, 0, st>>>(s->st, s->S1, s->S2, s->c2);
-        BSLS_LAUNCH_CHECK();
-    }
-    return BSLS_OK;
-}
-
-extern "C" int bsls_lbfgs_ls_finish(const bsls_bb_problem *p, const bsls_ls_state *s,
-                                    double *y_out, double *s_out, void *stream) {
-    int rc = check_problem_float(p);
-    if (rc != BSLS_OK || (rc = check_ls(s)) != BSLS_OK) return rc;
-    constexpr int LS_GRID = 512;
-    const int g = grid_for(p->nz, 256);
-    ls_finish_kernel<<<g < LS_GRID ? g : LS_GRID, 256, 0, (hipStream_t)stream>>>(
-        s->d, s->gx, s->gpt, p->nz, s->st, y_out, s_out, s->part, s->tickets);
-    BSLS_LAUNCH_CHECK();
-    return BSLS_OK;
-}
+// the engine's tenants, on the launchers above: LBFGS.solve's line search and DORE
+#include "bb_ls.hpp"
+#include "bb_dore.hpp"
 
 #ifdef BSLS_PHASE_STAMPS
 // the stamps of the last launches: [kernel][workgroup][slot] -> host (after a sync)
@@ -2209,16 +1746,10 @@ extern "C" int bsls_bb_stage(const bsls_bb_problem *p, int stage, int64_t iter, 
         case 0:  // reset scalars and tickets
             BSLS_CHECK(hipMemsetAsync(P.scal, 0, BSLS_S_COUNT * sizeof(double), st));
             BSLS_CHECK(hipMemsetAsync(P.work, 0, (size_t)((char *)w.p1 - (char *)P.work), st));
-            if (P.fx_sums) BSLS_CHECK(hipMemsetAsync(w.rmax, 0, RMAX_SLOTS * 8, st));
+            BSLS_CHECK(clear_rmax(P, w, st));
             return BSLS_OK;
         case 1:  // r_partial = A_g x_g (+ target on the shard_role 1 rank)
-            if (P.shard_role == 1) {
-                if (iter > 0) launch_k1<true, false, true>(P, iter, w, st);
-                else launch_k1<true, false, false>(P, iter, w, st);
-            } else {
-                if (iter > 0) launch_k1<false, false, true>(P, iter, w, st);
-                else launch_k1<false, false, false>(P, iter, w, st);
-            }
+            launch_k1_partial(P, iter, w, st);
             break;
         case 2:  // r += target, ||r||^2, stop test
         case 9:  // ||r||^2, stop test (r already the residual)
@@ -2245,8 +1776,7 @@ extern "C" int bsls_bb_stage(const bsls_bb_problem *p, int stage, int64_t iter, 
             break;
         case 14:  // stage 1 after stage 15 (r already initialised when it folds)
             if (iter <= 0) return BSLS_E_ARG;
-            if (P.shard_role == 1) launch_k1<true, false, true>(P, iter, w, st, 0, -1, k1_init_folded(P));
-            else launch_k1<false, false, true>(P, iter, w, st, 0, -1, k1_init_folded(P));
+            launch_k1_partial(P, iter, w, st, 0, -1, k1_init_folded(P));
             break;
         case 12:  // f / stopping test of iteration iter - 1 (after the sums' all-reduce)
             if (iter <= 0) return BSLS_E_ARG;
@@ -2270,7 +1800,7 @@ extern "C" int bsls_bb_stage(const bsls_bb_problem *p, int stage, int64_t iter, 
             break;
         case 7:  // single GCD K1: r = A x + target, ||r||^2, stop test (iter > 0)
             // (fx_sums: outside an iteration no K3 has cleared max|r| for this finish)
-            if (P.fx_sums && iter <= 0) BSLS_CHECK(hipMemsetAsync(w.rmax, 0, RMAX_SLOTS * 8, st));
+            if (iter <= 0) BSLS_CHECK(clear_rmax(P, w, st));
             if (iter > 0) launch_k1<true, true, true>(P, iter, w, st);
             else launch_k1<true, true, false>(P, iter, w, st);
             break;
@@ -2296,14 +1826,7 @@ extern "C" int bsls_bb_residual_rows(const bsls_bb_problem *p, int64_t iter, int
     const bsls_bb_problem &P = *p;
     if (rb0 < 0 || rb1 <= rb0 || rb1 > k1_row_blocks(P)) return BSLS_E_ARG;
     const BBWork w = bb_layout(P);
-    hipStream_t st = (hipStream_t)stream;
-    if (P.shard_role == 1) {
-        if (iter > 0) launch_k1<true, false, true>(P, iter, w, st, rb0, rb1);
-        else launch_k1<true, false, false>(P, iter, w, st, rb0, rb1);
-    } else {
-        if (iter > 0) launch_k1<false, false, true>(P, iter, w, st, rb0, rb1);
-        else launch_k1<false, false, false>(P, iter, w, st, rb0, rb1);
-    }
+    launch_k1_partial(P, iter, w, (hipStream_t)stream, rb0, rb1);
     BSLS_LAUNCH_CHECK();
     return BSLS_OK;
 }
@@ -2322,7 +1845,7 @@ extern "C" int bsls_bb_prologue(const bsls_bb_problem *p, void *stream) {
     if ((e = bsls_bb_stage(p, 3, 0, stream)) != BSLS_OK) return e;  // g_prev -> g[0]
     if ((e = bsls_bb_stage(p, 6, 0, stream)) != BSLS_OK) return e;
     // (fx_sums: max|r| of r(z0 + 1) was K2's; r(z0)'s alone is iteration 1's)
-    if (P.fx_sums) BSLS_CHECK(hipMemsetAsync(w.rmax, 0, RMAX_SLOTS * 8, st));
+    BSLS_CHECK(clear_rmax(P, w, st));
     launch_k1<true, true, false>(P, 0, w, st);  // r(z0), f(z0)
     BSLS_LAUNCH_CHECK();
     return BSLS_OK;
@@ -2371,11 +1894,7 @@ extern "C" int bsls_bb_k1_rows(const bsls_bb_problem *p, int64_t iter, int64_t r
     if (rc != BSLS_OK) return rc;
     const bsls_bb_problem &P = *p;
     if (iter <= 0 || rb0 < 0 || rb1 <= rb0 || rb1 > k1_row_blocks(P)) return BSLS_E_ARG;
-    const BBWork w = bb_layout(P);
-    hipStream_t st = (hipStream_t)stream;
-    const bool folded = k1_init_folded(P);
-    if (P.shard_role == 1) launch_k1<true, false, true>(P, iter, w, st, rb0, rb1, folded);
-    else launch_k1<false, false, true>(P, iter, w, st, rb0, rb1, folded);
+    launch_k1_partial(P, iter, bb_layout(P), (hipStream_t)stream, rb0, rb1, k1_init_folded(P));
     BSLS_LAUNCH_CHECK();
     return BSLS_OK;
 }

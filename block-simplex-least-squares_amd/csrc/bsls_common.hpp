@@ -174,6 +174,24 @@ __device__ bool last_of_sum(const double (&mine)[NV], double *partials, unsigned
     return true;
 }
 
+// The arrival half of the same hand-off for the G workgroups of row block rb,
+// which published their partials themselves (sc1 stores, drained, a barrier):
+// thread 0 takes ticket tk[rb] and the last of the G re-zeroes it; true, after
+// a barrier and the acquire that keeps the loads below the ticket, in the last
+// arriver's every thread.  flag: a __shared__ int of the caller's.
+__device__ __forceinline__ bool rowblock_last(unsigned *tk, int64_t rb, int64_t G, int *flag) {
+    if (threadIdx.x == 0) {
+        const unsigned prev =
+            __hip_atomic_fetch_add(&tk[rb], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        *flag = (prev == (unsigned)G - 1);
+        if (*flag) __hip_atomic_store(&tk[rb], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    __syncthreads();
+    if (!*flag) return false;
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    return true;
+}
+
 // last_block_sum with some slots reduced by max instead of sum (bit k of
 // MAXMASK): NaN-propagating max, fixed order like the sums.  `red` must hold
 // NV * (blockDim.x / 64) doubles.

@@ -136,15 +136,7 @@ __global__ __launch_bounds__(1024) void lsq_k1(bsls_panels M, int64_t m,
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();
-    if (threadIdx.x == 0) {
-        const unsigned prev =
-            __hip_atomic_fetch_add(&tkrb[rb], 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        row_last = (prev == (unsigned)G - 1);
-        if (row_last) __hip_atomic_store(&tkrb[rb], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    __syncthreads();
-    if (!row_last) return;
-    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+    if (!rowblock_last(tkrb, rb, G, &row_last)) return;
     const int64_t r0 = rb * PANEL_WAVES * M.prow;
     const int64_t r1 = (r0 + PANEL_WAVES * M.prow < m) ? r0 + PANEL_WAVES * M.prow : m;
     double sq[1] = {0.0};

@@ -22,11 +22,6 @@
 #ifndef BSLS_K3_KO
 #define BSLS_K3_KO 0
 #endif
-// BSLS_K3_REPAIR: K3's warm start repairs a failed partition
-// (pava_warm_repair) instead of running the reference passes from scratch
-#ifndef BSLS_K3_REPAIR
-#define BSLS_K3_REPAIR 1
-#endif
 
 namespace bsls {
 
@@ -328,10 +323,10 @@ __device__ __forceinline__ void pava_v1_wave_pair(double &ya, int La, uint64_t B
 // lane its run's prefix sum, the run sum comes from the run's last lane, and
 // two comparisons per lane decide.  If every lane passes, the fit is the run
 // means (sums in a tree order: within ulps of the reference's pooled
-// roundings); otherwise the pack runs the reference passes.  Comparisons that
-// fail only by rounding send the pack to the reference passes (still exact);
-// comparisons that pass only by rounding give a fit within ulps of the exact
-// one.  H must contain B (bit 0 set) and no bit at or above L.
+// roundings); otherwise the pack runs the reference passes from a repaired
+// partition (pava_warm_repair).  Comparisons that fail only by rounding send
+// the pack to the reference passes (still exact); comparisons that pass only
+// by rounding give a fit within ulps of the exact one.
 template <int CTRL, int RM>
 __device__ __forceinline__ double dpp_mov_d(double v) {
     const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(v), CTRL, RM, 0xF, true);
@@ -339,7 +334,7 @@ __device__ __forceinline__ double dpp_mov_d(double v) {
     return __hiloint2double(hi, lo);
 }
 
-// The test of a kept partition H, shared by both warm forms: this lane's run
+// The test of a kept partition H: this lane's run
 // [h, e], the run's mean m, and the two conditions (split: the prefix of the
 // run up to this lane has a mean >= m; order: a run head's mean is >= the
 // previous run's within its block).
@@ -379,15 +374,9 @@ __device__ __forceinline__ WarmTest warm_test(double y, int L, uint64_t B, uint6
     return WarmTest{h, e, m, split_ok, ok};
 }
 
-__device__ __forceinline__ bool pava_warm(double &y, int L, uint64_t B, uint64_t H) {
-    const WarmTest w = warm_test(y, L, B, H);
-    if (ballot_b(!w.ok) != 0ull) return false;
-    if (lane_id() < L) y = w.m;
-    return true;
-}
-
-// The warm start with repair (round 5): as pava_warm, but a pack whose kept
-// partition fails does not start over from single elements.  A kept run that
+// The warm start with repair (round 5): a pack whose kept partition holds
+// takes its run means; one whose kept partition fails does not start over
+// from single elements.  A kept run that
 // still cannot be split (its every proper prefix mean >= its mean: alone it
 // is one level of its own isotonic fit) is a state the reference's pooling
 // can reach from single elements, and pooling adjacent violators from any
@@ -395,11 +384,14 @@ __device__ __forceinline__ bool pava_warm(double &y, int L, uint64_t B, uint64_t
 // be split go back to their elements, and the reference passes run from
 // there -- usually one or two instead of ~4 from scratch.  The fit is the
 // unique PAVA fit up to the roundings of the kept runs' tree-order sums (the
-// north star's 1e-12, as pava_warm).  Returns false when the kept partition
+// north star's 1e-12).  Returns false when the kept partition
 // held (y = its run means, nothing to store), true when the passes ran
 // (y = the expanded fit, *heads = its run-head mask).  ys / ps / cst: as
-// pava_v1_wave_c.  H as pava_warm.  CPU model over the oracle's weighted
-// PAVA: tests/test_pava_repair_model.py.
+// pava_v1_wave_c.  H must contain B (bit 0 set) and no bit at or above L.
+// CPU model over the oracle's weighted PAVA: tests/test_pava_repair_model.py.
+// (The form without repair -- a failed partition ran the reference passes
+// from scratch -- measured slower, profiles/r05_k3_repair_ab.log; it last
+// existed at commit 36c7740.)
 __device__ __forceinline__ bool pava_warm_repair(double &y, int L, uint64_t B, uint64_t H,
                                                  double *ys, int *ps, int *cst, uint64_t *heads) {
     const int l = lane_id();

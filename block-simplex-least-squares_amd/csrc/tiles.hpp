@@ -163,17 +163,14 @@ __device__ __forceinline__ uint32_t tri_entry(const tile_tri &t, int j) {
 #ifndef BSLS_TILE_D
 #define BSLS_TILE_D 1
 #endif
-// BSLS_WALK_PREFILL: the dealt walk issues its first loads (wave_off /
-// group_col, then the P ring steps of entries and bases) BEFORE the caller's
-// `mid` step -- the clear of the LDS row sums and its barrier -- so the clear
-// runs under those loads instead of in front of them; the gathers and the LDS
-// adds start after it.  The same adds into the same zeroed rows.  A tile with
-// fewer than P steps (or none) loads only the steps it has, as before.  The
-// thread-stream walk (layout 0) runs `mid` first.  0: `mid` first everywhere
-// (A/B variant).
-#ifndef BSLS_WALK_PREFILL
-#define BSLS_WALK_PREFILL 1
-#endif
+// The dealt walk issues its first loads (wave_off / group_col, then the P
+// ring steps of entries and bases) BEFORE the caller's `mid` step -- the clear
+// of the LDS row sums and its barrier -- so the clear runs under those loads
+// instead of in front of them; the gathers and the LDS adds start after it.
+// The same adds into the same zeroed rows.  A tile with fewer than P steps (or
+// none) loads only the steps it has.  The thread-stream walk (layout 0) runs
+// `mid` first.  (`mid` first everywhere, the A/B variant of
+// profiles/handoff_ab.txt, last existed at commit 36c7740.)
 struct TileNoMid {
     __device__ __forceinline__ void operator()() const {}
 };
@@ -275,8 +272,10 @@ __device__ __forceinline__ void tile_walk_dealt(const bsls_tiles &T, int64_t rb,
                                                 const double *rcol, double fxs = 1.0,
                                                 double fxin = 1.0, MID mid = MID()) {
     static_assert(D >= 1 && D < P, "gathers run ahead of the entry loads");
-    if (BSLS_TILE_KO == 3 || !BSLS_WALK_PREFILL) mid();
-    if (BSLS_TILE_KO == 3) return;
+    if (BSLS_TILE_KO == 3) {
+        mid();
+        return;
+    }
     typedef typename TileEnt<PK3>::type ent_t;
     const int lane = threadIdx.x & 63;
     const int wv = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -309,7 +308,7 @@ __device__ __forceinline__ void tile_walk_dealt(const bsls_tiles &T, int64_t rb,
         ring[k] = (k < nq) ? ld(k) : ent_t{};
         bring[k] = (k < nq) ? Bq[(int64_t)k * 16] : int4{0, 0, 0, 0};
     }
-    if (BSLS_WALK_PREFILL) mid();   // (the caller's LDS clear and barrier, under the loads above)
+    mid();   // (the caller's LDS clear and barrier, under the loads above)
     // v[d] / a[d]: the gathered values (and stored values) of step s + d
     double v[D + 1][4], a[D + 1][4];
     double ko = 0.0;

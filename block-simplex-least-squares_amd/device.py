@@ -1121,7 +1121,7 @@ class BBEngine:
         P.max_iter = int(opts.get('max_iter', 300000))
         P.opt_tol = float(opts.get('opt_tol', 1e-6))
         P.early_exit = 1 if early_exit else 0
-        # K3's warm start (pava_wave.hpp pava_warm: within ulps of the reference
+        # K3's warm start (pava_wave.hpp pava_warm_repair: within ulps of the reference
         # PAVA, not bit-identical): on unless deterministic; BSLS_K3_WARM=0/1
         warm = os.environ.get('BSLS_K3_WARM')
         P.pava_warm = int(warm) if warm is not None else (0 if deterministic else 1)

@@ -1,6 +1,6 @@
 """Partition stability of K3's PAVA between BB iterations (CPU, oracle replay):
 the share of blocks / packs whose final run partition equals the previous
-iteration's -- the case for K3's warm start (pava_wave.hpp pava_warm).
+iteration's -- the case for K3's warm start (pava_wave.hpp pava_warm_repair).
 python tools/k3_warm.py [n]"""
 import os, sys
 import numpy as np

@@ -1,4 +1,4 @@
-"""numpy model of K3's warm-start test (pava_wave.hpp pava_warm): the same
+"""numpy model of K3's warm-start test (pava_wave.hpp warm_test): the same
 segmented scan (row_shr 1/2/4/8, row_bcast 15/31 with the per-step segment
 test), split and order conditions, on random packs: every true PAVA partition
 must pass, and no partition may pass with a fit further than 1e-12 from PAVA's."""

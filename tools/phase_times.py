@@ -15,8 +15,8 @@ kernel's first entry stamp to the workgroups' median / last stamp of the
 phase's end.  The stamp buffer holds the first 4096 workgroups of a launch
 (bb_k3 at C3 launches 4.2k: the later ones are not in its figures, and the
 output says how many were read).  Slot 2 of the walks is taken where the LDS
-clear starts: with BSLS_WALK_PREFILL the walk's first loads are issued by
-then, without it none is.  The stamps cost a few scalar instructions each; the build's
+clear starts: the dealt walk's first loads are issued by then (tiles.hpp
+tile_walk_dealt).  The stamps cost a few scalar instructions each; the build's
 iteration is timed against nothing here -- the figures attribute, they do not
 benchmark.
 """
