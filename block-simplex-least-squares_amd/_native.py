@@ -157,6 +157,9 @@ _SIGS = {
                                    _vp]),
     'bsls_isotonic_pack_plan': (_i64, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _i64]),
     'bsls_isotonic_packs': (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _sz, _vp]),
+    'bsls_isotonic_packs_fast': (_int, [_vp, _vp, _vp, _vp, _i64, _vp, _i64, _i64, _vp, _sz,
+                                        _vp]),
+    'bsls_isotonic_multi_fast': (_int, [_vp, _vp, _i64, _i64, _i64, _vp, _sz, _vp]),
     'bsls_x2z': (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     'bsls_z2x': (_int, [_vp, _vp, _vp, _i64, _i64, _vp]),
     'bsls_n_apply': (_int, [_vp, _vp, _vp, _i64, _i64, _int, _vp]),

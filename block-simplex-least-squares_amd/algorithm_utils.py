@@ -60,8 +60,12 @@ class BlockProj:
     """proj_multi_simplex_c / proj_multi_ball_c / PAVA+clip on a device vector,
     in place (the reference's proj closures mutate x and return None)."""
 
-    def __init__(self, block_starts, n, kind='simplex', flows=None):
+    def __init__(self, block_starts, n, kind='simplex', flows=None, fast=None):
+        """fast (kind='pava' only): True / False for the prefix-sum or the
+        bit-identical PAVA, None to read BSLS_ISO at every call
+        (device.iso_mode)."""
         torch = _torch()
+        self.fast = fast
         L = _native.lib()
         st = np.ascontiguousarray(block_starts, dtype=np.int64)
         _check_starts(st, n)
@@ -99,9 +103,15 @@ class BlockProj:
                                          self.max_block, ptr(self.ws), self.ws.numel(),
                                          stream_handle()), 'bsls_proj_multi_ball')
         else:
-            check(L.bsls_isotonic_multi(1, ptr(x), ptr(self.starts), self.p, self.n, None, 1,
-                                        self.max_block, ptr(self.ws), self.ws.numel(), None,
-                                        stream_handle()), 'bsls_isotonic_multi')
+            from device import iso_mode
+            if iso_mode(self.fast):
+                check(L.bsls_isotonic_multi_fast(ptr(x), ptr(self.starts), self.p, self.n,
+                                                 self.max_block, ptr(self.ws), self.ws.numel(),
+                                                 stream_handle()), 'bsls_isotonic_multi_fast')
+            else:
+                check(L.bsls_isotonic_multi(1, ptr(x), ptr(self.starts), self.p, self.n, None, 1,
+                                            self.max_block, ptr(self.ws), self.ws.numel(), None,
+                                            stream_handle()), 'bsls_isotonic_multi')
             torch.clamp(x, 0.0, 1.0, out=x)     # np.maximum(0.,x,x); np.minimum(1.,x,x)
         if self.flows is not None:
             torch.mul(x, self.flows, out=x)

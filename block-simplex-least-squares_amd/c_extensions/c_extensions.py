@@ -25,7 +25,9 @@ Projections (proj_simplex_c, proj_multi_simplex_c, proj_multi_ball_c) take the
 sorting kernels, which reproduce the reference bit for bit; BSLS_PROJ=fast
 selects the sort-free ones (bsls_proj_multi_*_fast: within 1e-12 * max(1,
 |ref|), the north star's projection contract -- measured no faster on C2,
-DESIGN.md §4).
+DESIGN.md §4).  isotonic_regression_multi_c's plain call (weight=None,
+update=1) likewise replays the reference bit for bit; BSLS_ISO=fast selects the
+prefix-sum form (bsls_isotonic_packs_fast, the same contract).
 """
 import os
 
@@ -242,6 +244,11 @@ def _weights(weight, n, first):
 
 
 def _run_iso(variant, y, blocks_h, n, weight, update, name):
+    from device import iso_mode, iso_plan
+    # BSLS_ISO (read per call, as BSLS_PROJ): the planned variant-1 call below
+    # follows it; every other variant / weight / update combination and the
+    # host path stay on the bit-identical code, the value still validated
+    fast = iso_mode()
     if _cpu_sel(y, weight):
         return _cpu.isotonic(variant, y, blocks_h, n, weight, update)
     torch = _torch()
@@ -249,9 +256,8 @@ def _run_iso(variant, y, blocks_h, n, weight, update, name):
     if variant == 1 and weight is None and update:
         # main.py's call (fresh unit run lengths, expanded): the layout's pack
         # plan, made once and cached by content (device.iso_plan), one launch
-        from device import iso_plan
         st = _Staged(y)
-        iso_plan(np.asarray(blocks_h, dtype=np.int64), n).apply(st.dev)
+        iso_plan(np.asarray(blocks_h, dtype=np.int64), n).apply(st.dev, fast=fast)
         st.commit()
         return
     st = _Staged(y)

@@ -20,6 +20,7 @@
 #include "pava.hpp"
 #include "pava_long.hpp"
 #include "pava_wave.hpp"
+#include "pava_fast.hpp"
 
 namespace bsls {
 
@@ -123,17 +124,21 @@ __global__ __launch_bounds__(256) void iso_plan_kernel(const int64_t *__restrict
 }
 
 // one wave-parallel PAVA v1 (unit weights, expand) over y[s0, s0 + L), L <= 64,
-// blocks starting at the set bits of B
+// blocks starting at the set bits of B.  FAST: the prefix-sum form
+// (pava_fast.hpp, ys = 128 doubles) in place of the reference's passes
+template <bool FAST>
 __device__ __forceinline__ void iso_wave_pack(double *__restrict__ y, int64_t s0, int L,
                                               uint64_t B, double *ys, int *ps, int *cst) {
     const int l = lane_id();
     double v = (l < L) ? y[s0 + l] : 0.0;
-    pava_v1_wave_c(v, L, B, ys, ps, cst);
+    if constexpr (FAST) pava_fast_wave(v, L, B, ys, ys + WAVE);
+    else pava_v1_wave_c(v, L, B, ys, ps, cst);
     if (l < L) y[s0 + l] = v;
 }
 
 // window blocks [f, e): one pack of <= 63 elements, the last block on its own
 // when it is longer than the window
+template <bool FAST>
 __device__ __forceinline__ void iso_window(double *__restrict__ y,
                                            const int64_t *__restrict__ starts, int64_t nb,
                                            int64_t n, int64_t f, int64_t e,
@@ -151,12 +156,12 @@ __device__ __forceinline__ void iso_window(double *__restrict__ y,
         ps[l] = 0;
         if (l < nsm) ps[(int)(starts[f + l] - s0)] = 1;
         const uint64_t B = __ballot(l < L && ps[l] != 0);
-        iso_wave_pack(y, s0, L, B, ys, ps, cst);
+        iso_wave_pack<FAST>(y, s0, L, B, ys, ps, cst);
     }
     if (big) {
         const int64_t len = el - sl;
         if (len <= WAVE) {
-            iso_wave_pack(y, sl, (int)len, 1ull, ys, ps, cst);
+            iso_wave_pack<FAST>(y, sl, (int)len, 1ull, ys, ps, cst);
         } else if (l == 0) {
             llist[atomicAdd(lcnt, 1)] = (int32_t)(e - 1);   // iso_long_kernel's
         }
@@ -164,7 +169,10 @@ __device__ __forceinline__ void iso_window(double *__restrict__ y,
 }
 
 // wave q: windows 2q and 2q + 1 -- as one pack when their blocks span <= 64
-// elements (the common case), else window by window
+// elements (the common case), else window by window.  FAST
+// (bsls_isotonic_multi_fast): the same windows and packs through
+// pava_fast_wave, a pair of packs one after the other
+template <bool FAST>
 __global__ __launch_bounds__(256) void iso_pack_kernel(double *__restrict__ y,
                                                        const int64_t *__restrict__ starts,
                                                        int64_t nb, int64_t n, int64_t nwin,
@@ -177,6 +185,8 @@ __global__ __launch_bounds__(256) void iso_pack_kernel(double *__restrict__ y,
     __shared__ double pv_y[4][64];
     __shared__ int pv_p[4][128];
     __shared__ int pv_c[4][65];
+    __shared__ double pv_f[FAST ? 4 : 1][2 * WAVE];   // pava_fast_wave's (no use, no LDS, in the exact form)
+#define ISO_YS (FAST ? pv_f[FAST ? wv : 0] : pv_y[wv])
     const int64_t p0 = 2 * q;
     if (p0 >= nwin) return;
     const int64_t f = win_first[p0];
@@ -191,7 +201,7 @@ __global__ __launch_bounds__(256) void iso_pack_kernel(double *__restrict__ y,
         ps[l] = 0;
         if (l < nbk) ps[(int)(starts[f + l] - s0)] = 1;
         const uint64_t B = __ballot(l < span && ps[l] != 0);
-        iso_wave_pack(y, s0, (int)span, B, pv_y[wv], ps, pv_c[wv]);
+        iso_wave_pack<FAST>(y, s0, (int)span, B, ISO_YS, ps, pv_c[wv]);
     } else {
         // two packs, one per window; with no long last block (the common
         // case) both run in the wave together, sharing their passes after
@@ -211,14 +221,20 @@ __global__ __launch_bounds__(256) void iso_pack_kernel(double *__restrict__ y,
             const uint64_t Bb = __ballot(l < Lb && ps[l] != 0);
             double va = (l < La) ? y[sa + l] : 0.0;
             double vb = (l < Lb) ? y[sb + l] : 0.0;
-            pava_v1_wave_pair(va, La, Ba, vb, Lb, Bb, pv_y[wv], ps, pv_c[wv]);
+            if constexpr (FAST) {
+                pava_fast_wave(va, La, Ba, ISO_YS, ISO_YS + WAVE);
+                pava_fast_wave(vb, Lb, Bb, ISO_YS, ISO_YS + WAVE);
+            } else {
+                pava_v1_wave_pair(va, La, Ba, vb, Lb, Bb, pv_y[wv], ps, pv_c[wv]);
+            }
             if (l < La) y[sa + l] = va;
             if (l < Lb) y[sb + l] = vb;
         } else {
-            iso_window(y, starts, nb, n, f, m, lcnt, llist, pv_y[wv], ps, pv_c[wv]);
-            iso_window(y, starts, nb, n, m, e, lcnt, llist, pv_y[wv], ps, pv_c[wv]);
+            iso_window<FAST>(y, starts, nb, n, f, m, lcnt, llist, ISO_YS, ps, pv_c[wv]);
+            iso_window<FAST>(y, starts, nb, n, m, e, lcnt, llist, ISO_YS, ps, pv_c[wv]);
         }
     }
+#undef ISO_YS
 }
 
 // one workgroup per listed long block (> 64 elements), grid-strided
@@ -282,6 +298,28 @@ __global__ __launch_bounds__(256) void iso_packs_kernel(double *__restrict__ y,
 #pragma unroll
     for (int q = 0; q < PPW; ++q)
         if (l < L[q] && L[q] <= WAVE) y[s0[q] + l] = v[q];
+}
+
+// The planned packs through pava_fast_wave (bsls_isotonic_packs_fast): one
+// pack per wave; a wave past the last pack, or on a long pack
+// (iso_long_planned's), has nothing to do.
+__global__ __launch_bounds__(256) void iso_packs_fast_kernel(double *__restrict__ y,
+                                                             const int64_t *__restrict__ pk_start,
+                                                             const int64_t *__restrict__ pk_mask,
+                                                             const int32_t *__restrict__ pk_len,
+                                                             int64_t npacks) {
+    const int l = lane_id();
+    const int wv = threadIdx.x / WAVE;
+    const int64_t pk = __builtin_amdgcn_readfirstlane((int)blockIdx.x * 4 + wv);
+    __shared__ double pv_f[4][2 * WAVE];
+    if (pk >= npacks) return;
+    const int64_t s0 = pk_start[pk];
+    const uint64_t B = (uint64_t)pk_mask[pk];
+    const int L = pk_len[pk];
+    if (L < 1 || L > WAVE) return;
+    double v = (l < L) ? y[s0 + l] : 0.0;
+    pava_fast_wave(v, L, B, pv_f[wv], pv_f[wv] + WAVE);
+    if (l < L) y[s0 + l] = v;
 }
 
 // one workgroup per long block of the plan (> 64 elements), grid-strided
@@ -374,6 +412,26 @@ extern "C" int bsls_isotonic_packs(double *d_y, const int64_t *d_pk_start, const
     return BSLS_OK;
 }
 
+extern "C" int bsls_isotonic_packs_fast(double *d_y, const int64_t *d_pk_start,
+                                        const int64_t *d_pk_mask, const int32_t *d_pk_len,
+                                        int64_t npacks, const int32_t *d_long_packs, int64_t nlong,
+                                        int64_t n, void *d_work, size_t work_bytes, void *stream) {
+    if (!d_y || !d_pk_start || !d_pk_mask || !d_pk_len || npacks < 1 || n <= 0 || nlong < 0)
+        return BSLS_E_ARG;
+    if (nlong > 0 && (!d_long_packs || !d_work || work_bytes < bsls_isotonic_workspace_size(n)))
+        return BSLS_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    iso_packs_fast_kernel<<<grid_for(npacks, 4), 256, 0, st>>>(d_y, d_pk_start, d_pk_mask, d_pk_len,
+                                                               npacks);
+    BSLS_LAUNCH_CHECK();
+    if (nlong > 0) {
+        iso_long_planned<<<(int)(nlong < 1024 ? nlong : 1024), LONG_T, 0, st>>>(
+            d_y, d_pk_start, d_pk_len, d_long_packs, nlong, iso_layout(d_work, n));
+        BSLS_LAUNCH_CHECK();
+    }
+    return BSLS_OK;
+}
+
 extern "C" size_t bsls_isotonic_workspace_size(int64_t n) {
     return iso_layout(nullptr, n).bytes;
 }
@@ -395,8 +453,8 @@ extern "C" int bsls_isotonic_multi(int variant, double *d_y, const int64_t *d_st
         iso_plan_kernel<<<grid_for(nblocks + 1, 256), 256, 0, st>>>(d_starts, nblocks, nwin,
                                                                     w.plan, w.lcnt);
         BSLS_LAUNCH_CHECK();
-        iso_pack_kernel<<<grid_for((nwin + 1) / 2, 4), 256, 0, st>>>(d_y, d_starts, nblocks, n, nwin,
-                                                                    w.plan, w.lcnt, w.llist);
+        iso_pack_kernel<false><<<grid_for((nwin + 1) / 2, 4), 256, 0, st>>>(
+            d_y, d_starts, nblocks, n, nwin, w.plan, w.lcnt, w.llist);
         BSLS_LAUNCH_CHECK();
         if (max_block > WAVE) {
             const int64_t most = n / (WAVE + 1) + 1;
@@ -413,5 +471,28 @@ extern "C" int bsls_isotonic_multi(int variant, double *d_y, const int64_t *d_st
     else
         iso_kernel<3><<<grid, WAVE, 0, st>>>(d_y, d_starts, nblocks, n, d_weight, expand, ws, d_status);
     BSLS_LAUNCH_CHECK();
+    return BSLS_OK;
+}
+
+extern "C" int bsls_isotonic_multi_fast(double *d_y, const int64_t *d_starts, int64_t nblocks,
+                                        int64_t n, int64_t max_block, void *d_work,
+                                        size_t work_bytes, void *stream) {
+    if (nblocks <= 0 || n <= 0 || !d_y || !d_starts) return BSLS_E_ARG;
+    if (!d_work || work_bytes < bsls_isotonic_workspace_size(n)) return BSLS_E_WORKSPACE;
+    hipStream_t st = (hipStream_t)stream;
+    const IsoWork w = iso_layout(d_work, n);
+    const int64_t nwin = iso_nwin(n);
+    iso_plan_kernel<<<grid_for(nblocks + 1, 256), 256, 0, st>>>(d_starts, nblocks, nwin, w.plan,
+                                                                w.lcnt);
+    BSLS_LAUNCH_CHECK();
+    iso_pack_kernel<true><<<grid_for((nwin + 1) / 2, 4), 256, 0, st>>>(d_y, d_starts, nblocks, n,
+                                                                       nwin, w.plan, w.lcnt, w.llist);
+    BSLS_LAUNCH_CHECK();
+    if (max_block > WAVE) {
+        const int64_t most = n / (WAVE + 1) + 1;
+        iso_long_kernel<<<(int)(most < 1024 ? most : 1024), LONG_T, 0, st>>>(d_y, d_starts, nblocks,
+                                                                             n, w);
+        BSLS_LAUNCH_CHECK();
+    }
     return BSLS_OK;
 }

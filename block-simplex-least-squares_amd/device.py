@@ -687,6 +687,19 @@ def lsq_operator(A, AT=None, general=False, k1=None, k2=None):
         return None
 
 
+def iso_mode(fast=None):
+    """True for the prefix-sum PAVA (bsls_isotonic_packs_fast / _multi_fast,
+    the 1e-12 contract), False for the bit-identical one.  fast=None reads
+    BSLS_ISO -- 'exact' (the default) or 'fast' -- per call, so a test or a
+    caller can switch; True / False override it.  Needs no GPU."""
+    if fast is not None:
+        return bool(fast)
+    mode = os.environ.get('BSLS_ISO', 'exact')
+    if mode not in ('fast', 'exact'):
+        raise ValueError('BSLS_ISO must be fast or exact, not %r' % mode)
+    return mode == 'fast'
+
+
 class IsoPlan:
     """A block layout's pack plan on the device (bsls_isotonic_pack_plan /
     bsls_isotonic_packs): isotonic_regression_multi_c's variant-1 call
@@ -708,16 +721,19 @@ class IsoPlan:
         self.work = (torch.zeros(L.bsls_isotonic_workspace_size(self.n), dtype=torch.uint8,
                                  device='cuda') if self.nlong else None)
 
-    def apply(self, y, stream=None):
-        """PAVA v1 (expanded) of every block of y[:n], in place."""
+    def apply(self, y, stream=None, fast=None):
+        """PAVA v1 (expanded) of every block of y[:n], in place: bit-identical
+        to the reference, or the prefix-sum form within 1e-12 (iso_mode(fast):
+        BSLS_ISO read per call when fast is None)."""
+        name = 'bsls_isotonic_packs_fast' if iso_mode(fast) else 'bsls_isotonic_packs'
         L = _native.lib()
         if y.device.index != self.device:
             raise ValueError('IsoPlan built on cuda:%d applied to a tensor on %s'
                              % (self.device, y.device))
-        check(L.bsls_isotonic_packs(ptr(y), ptr(self.start), ptr(self.mask), ptr(self.len),
-                                    self.npacks, ptr(self.longs), self.nlong, self.n,
-                                    ptr(self.work), self.work.numel() if self.work is not None
-                                    else 0, stream_handle(stream)), 'bsls_isotonic_packs')
+        check(getattr(L, name)(ptr(y), ptr(self.start), ptr(self.mask), ptr(self.len),
+                               self.npacks, ptr(self.longs), self.nlong, self.n,
+                               ptr(self.work), self.work.numel() if self.work is not None
+                               else 0, stream_handle(stream)), name)
         return y
 
 
@@ -1376,7 +1392,8 @@ class BBEngine:
 
     def proj(self, z):
         """isotonic_regression_multi_c on the z-blocks, then clip to [0, 1]
-        (main.py:61-65); returns a new tensor like np.maximum(np.minimum(..))."""
+        (main.py:61-65); returns a new tensor like np.maximum(np.minimum(..)).
+        The PAVA follows BSLS_ISO, read per call (IsoPlan.apply)."""
         torch = _torch()
         L = _native.lib()
         if self.layout.max_zblock < 1 or np.any(self.layout.sizes < 2):

@@ -89,6 +89,32 @@ int64_t bsls_isotonic_pack_plan(const int64_t *starts, int64_t nblocks, int64_t 
 int bsls_isotonic_packs(double *d_y, const int64_t *d_pk_start, const int64_t *d_pk_mask,
                         const int32_t *d_pk_len, int64_t npacks, const int32_t *d_long_packs,
                         int64_t nlong, int64_t n, void *d_work, size_t work_bytes, void *stream);
+/* The same planned call (same arguments, workspace rule, errors and pack plan)
+ * without replaying the reference's pooling order (isotonic_regression.h:13-58,
+ * 85-92): the isotonic fit is unique, so each pack of <= 64 elements pools
+ * adjacent violators straight on a run-head mask, the run sums being
+ * differences of one block-segmented prefix sum taken in a fixed lane order
+ * (csrc/pava_fast.hpp).  Within 1e-12 * max(1, |reference|) of the reference
+ * on every tested input (the north star's projection contract), and on any
+ * finite input within 1e-12 * max(1, max |y| over the element's block) (a
+ * prefix sum of <= 64 terms errs by <= 63 u sum|y|; a difference of two,
+ * divided by a length >= 1, by <= 2 * 63 * 64 * 2^-53 max|y| = 9.0e-13 max|y|);
+ * deterministic, not bit-identical.  An element whose run has length 1 keeps
+ * its bits (an input already non-decreasing within every block comes back
+ * unchanged), the output is non-decreasing within every block exactly, and
+ * blocks longer than 64 take the bit-identical long-block kernel.  Non-finite
+ * input gives unspecified values in its block and cannot hang the call. */
+int bsls_isotonic_packs_fast(double *d_y, const int64_t *d_pk_start, const int64_t *d_pk_mask,
+                             const int32_t *d_pk_len, int64_t npacks,
+                             const int32_t *d_long_packs, int64_t nlong, int64_t n, void *d_work,
+                             size_t work_bytes, void *stream);
+/* bsls_isotonic_multi's variant 1, weight = NULL, expand = 1 call
+ * (isotonic_regression.h:13-58,85-92) in the same form and under the same two
+ * bounds, on the device window plan of bsls_isotonic_multi (no host plan).  Its
+ * packs differ from the planned ones, so the prefix sums' lane order and the
+ * last bits may too.  The workspace is always required. */
+int bsls_isotonic_multi_fast(double *d_y, const int64_t *d_starts, int64_t nblocks, int64_t n,
+                             int64_t max_block, void *d_work, size_t work_bytes, void *stream);
 
 /* ---- z <-> x change of variables --------------------------------------------
  * Replaces x2z_c / z2x_c (c_extensions.pyx:195-248); d_starts[0] must be 0. */
