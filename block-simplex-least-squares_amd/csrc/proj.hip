@@ -280,13 +280,7 @@ __device__ __forceinline__ double chain_lambda(const Chain &c) {
 // KB > 16: top-16 selection networks (proj_net.hpp) + the early-settling
 // chain; a wave with an unsettled lane sorts fully (the networks only
 // permute, the -inf padding stays put).
-// THR (the sort-free path, bsls_proj_multi_*_fast): no sort and no chain --
-// Michelot's threshold iteration on the lane's registers: from the lower
-// bound tau = max(M - 1, (S - 1) / k) (M the block max, S its sum) each pass
-// sums the entries above tau and sets tau = (sum - 1) / count; the active
-// set only shrinks, and once its count repeats tau is the projection's
-// threshold.  Within ulps of the sorted chain (the north star's 1e-12).
-template <int N, int KB, bool BALL, bool THR = false>
+template <int N, int KB, bool BALL>
 __device__ __forceinline__ void lane_block_lds(double *buf, int off, int k, int lane) {
     double v[N];
     double acc = 0.0;
@@ -309,37 +303,7 @@ __device__ __forceinline__ void lane_block_lds(double *buf, int off, int k, int 
     }
     const bool need = BALL ? (acc > 1.0) : true;
     double lam = 0.0;
-    if constexpr (THR) {
-        if (!BALL || __builtin_amdgcn_ballot_w64(need)) {
-            double M = -INFINITY, S = 0.0;
-#pragma unroll
-            for (int j = 0; j < KB; ++j) {
-                M = fmax(M, v[j]);
-                S += (j < k) ? v[j] : 0.0;
-            }
-            double tau = fmax(M - 1.0, (S - 1.0) / (double)(k > 0 ? k : 1));
-            bool done = (k == 0) || !need;
-            int cp = -1;
-            for (int it = 0; it <= KB + 1; ++it) {
-                if (__builtin_amdgcn_ballot_w64(!done) == 0ull) break;
-                double sa = 0.0;
-                int c = 0;
-#pragma unroll
-                for (int j = 0; j < KB; ++j) {
-                    const bool a = v[j] > tau;
-                    sa += a ? v[j] : 0.0;
-                    c += a ? 1 : 0;
-                }
-                const double tn = (sa - 1.0) / (double)(c > 0 ? c : 1);
-                if (!done) {
-                    done = (c == cp);
-                    tau = tn;
-                    cp = c;
-                }
-            }
-            lam = -tau;
-        }
-    } else if (!BALL || __builtin_amdgcn_ballot_w64(need)) {
+    if (!BALL || __builtin_amdgcn_ballot_w64(need)) {
         bool full = true;
         if constexpr (KB > 16) {
             // level 1: the 16 largest, sorted, and the chain over them;
@@ -377,17 +341,6 @@ __device__ __forceinline__ void lane_block_lds(double *buf, int off, int k, int 
             }
         }
     }
-    if constexpr (THR) {
-        // nothing was sorted: v[j] (clamped for the ball, as the output wants)
-        // is still entry j, so no second read of the block
-#pragma unroll
-        for (int j = 0; j < KB; ++j) {
-            const double t = v[j];
-            const double r = need ? relu_ref(lam + t) : t;
-            buf[(j < k) ? off + j : PCAP + WAVE + 2 + lane] = r;
-        }
-        return;
-    }
     asm volatile("" ::: "memory");   // keep the o[] loads after the sort (VGPRs)
     double o[KB];
 #pragma unroll
@@ -402,13 +355,18 @@ __device__ __forceinline__ void lane_block_lds(double *buf, int off, int k, int 
 }
 
 // One wave's group of 64 consecutive blocks (one lane each), staged in its
-// own LDS buffer.  W > 1 (proj_lds_kernel<BALL, W>, W waves per workgroup):
+// own LDS buffer.  A workgroup of proj_lds_kernel has LDS_WAVES waves:
 // wave w issues its range's loads only once wave w - 1's have landed
 // (`landed`, an LDS counter), so the waves of a CU pass through the load /
 // sort / store phases staggered instead of all together -- wave w's loads
 // stream while wave w - 1 sorts.  Every wave bumps the counter exactly once,
 // whatever path it takes, so no wave waits forever.
-template <bool BALL, int W, bool THR = false>
+// LDS_WAVES 2: C2 20.7 -> 20.2 us per launch against one wave per workgroup
+// (HBM-fed batch); 3 is slower (27.9 us: 60 KB of LDS per workgroup leave 512
+// slots for 521 workgroups, a tail).
+constexpr int LDS_WAVES = 2;
+
+template <bool BALL>
 __device__ __forceinline__ void lds_group(double *__restrict__ y,
                                           const int64_t *__restrict__ starts, int64_t nb,
                                           int64_t n, int64_t *__restrict__ big_list,
@@ -416,15 +374,11 @@ __device__ __forceinline__ void lds_group(double *__restrict__ y,
                                           double *buf, int *landed, int64_t grp, int wv,
                                           int lane) {
     auto wait_turn = [&]() {
-        if constexpr (W > 1) {
-            if (wv > 0)
-                while (__atomic_load_n(landed, __ATOMIC_RELAXED) < wv) __builtin_amdgcn_s_sleep(1);
-        }
+        if (wv > 0)
+            while (__atomic_load_n(landed, __ATOMIC_RELAXED) < wv) __builtin_amdgcn_s_sleep(1);
     };
     auto pass_turn = [&]() {
-        if constexpr (W > 1) {
-            if (lane == 0) __atomic_store_n(landed, wv + 1, __ATOMIC_RELAXED);
-        }
+        if (lane == 0) __atomic_store_n(landed, wv + 1, __ATOMIC_RELAXED);
     };
     const int64_t b0 = grp * WAVE;
     const int64_t b = b0 + lane;
@@ -486,24 +440,19 @@ __device__ __forceinline__ void lds_group(double *__restrict__ y,
         }
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    if constexpr (W == 1) {
-        __syncthreads();
-    } else {
-        // the wave reads only its own buffer: its DMA writes are complete at
-        // vmcnt(0), and its own LDS accesses execute in order
-        pass_turn();
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
+    // the wave reads only its own buffer: its DMA writes are complete at
+    // vmcnt(0), and its own LDS accesses execute in order
+    pass_turn();
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     const int off = (k > 0) ? (int)(s - s0) + sh : 0;
-    if (kmax <= 8) lane_block_lds<8, 8, BALL, THR>(buf, off, k, lane);
-    else if (kmax <= 16) lane_block_lds<16, 16, BALL, THR>(buf, off, k, lane);
-    else if (kmax <= 32) lane_block_lds<32, 32, BALL, THR>(buf, off, k, lane);
-    else if (kmax <= 40) lane_block_lds<64, 40, BALL, THR>(buf, off, k, lane);
-    else if (kmax <= 48) lane_block_lds<64, 48, BALL, THR>(buf, off, k, lane);
-    else if (kmax <= 56) lane_block_lds<64, 56, BALL, THR>(buf, off, k, lane);
-    else lane_block_lds<64, 64, BALL, THR>(buf, off, k, lane);
-    if constexpr (W == 1) __syncthreads();
-    else asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+    if (kmax <= 8) lane_block_lds<8, 8, BALL>(buf, off, k, lane);
+    else if (kmax <= 16) lane_block_lds<16, 16, BALL>(buf, off, k, lane);
+    else if (kmax <= 32) lane_block_lds<32, 32, BALL>(buf, off, k, lane);
+    else if (kmax <= 40) lane_block_lds<64, 40, BALL>(buf, off, k, lane);
+    else if (kmax <= 48) lane_block_lds<64, 48, BALL>(buf, off, k, lane);
+    else if (kmax <= 56) lane_block_lds<64, 56, BALL>(buf, off, k, lane);
+    else lane_block_lds<64, 64, BALL>(buf, off, k, lane);
+    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     // out: 16-B write-through (sc1) stores of the aligned pairs -- the bytes
     // leave L2 while other waves still compute, instead of as dirty lines at
     // the kernel's end (measured -2.8 us at C2) -- and the unaligned head /
@@ -534,29 +483,24 @@ __device__ __forceinline__ void lds_group(double *__restrict__ y,
     }
 }
 
-// (64 W, 2): at most 256 VGPRs so two waves fit per SIMD -- the whole C2 grid
-// (~6 waves per CU) is then resident at once.
-template <bool BALL, int W, bool THR = false>
-__global__ __launch_bounds__(64 * W, 2) void proj_lds_kernel(double *__restrict__ y,
-                                                          const int64_t *__restrict__ starts,
-                                                          int64_t nb, int64_t n,
-                                                          int64_t *__restrict__ big_list,
-                                                          unsigned *__restrict__ big_count,
-                                                          int allow_big,
-                                                          const double *__restrict__ gate) {
-    __shared__ __attribute__((aligned(16))) double buf[W][PBUF];
+// (64 LDS_WAVES, 2): at most 256 VGPRs so two waves fit per SIMD -- the whole
+// C2 grid (~6 waves per CU) is then resident at once.
+template <bool BALL>
+__global__ __launch_bounds__(64 * LDS_WAVES, 2) void proj_lds_kernel(
+    double *__restrict__ y, const int64_t *__restrict__ starts, int64_t nb, int64_t n,
+    int64_t *__restrict__ big_list, unsigned *__restrict__ big_count, int allow_big,
+    const double *__restrict__ gate) {
+    __shared__ __attribute__((aligned(16))) double buf[LDS_WAVES][PBUF];
     __shared__ int landed;
     // gated launch (the x-space BB engine, xbb.hip): run only when *gate == 1
     // (its STEP mode); the big-block kernels then find an empty list too
     if (gate && *gate != 1.0) return;
-    const int wv = (W == 1) ? 0 : (int)(threadIdx.x / WAVE);
-    const int lane = (W == 1) ? (int)threadIdx.x : (int)(threadIdx.x % WAVE);
-    if constexpr (W > 1) {
-        if (threadIdx.x == 0) landed = 0;
-        __syncthreads();
-    }
-    lds_group<BALL, W, THR>(y, starts, nb, n, big_list, big_count, allow_big, buf[wv], &landed,
-                            (int64_t)blockIdx.x * W + wv, wv, lane);
+    const int wv = (int)(threadIdx.x / WAVE);
+    const int lane = (int)(threadIdx.x % WAVE);
+    if (threadIdx.x == 0) landed = 0;
+    __syncthreads();
+    lds_group<BALL>(y, starts, nb, n, big_list, big_count, allow_big, buf[wv], &landed,
+                    (int64_t)blockIdx.x * LDS_WAVES + wv, wv, lane);
 }
 
 // In-place descending bitonic sort of u[0..P) by the whole workgroup
@@ -774,11 +718,9 @@ __global__ __launch_bounds__(HUGE_THREADS) void proj_huge_apply(
 // Passes (C2): 5 * N(0,1) blocks 1-2 (tau_0 is usually exact), U[0,1) ~5.
 // A set of one element (rho = 0) reproduces 1 - u_0 bit for bit.
 //
-// Lane mapping: LPB lanes per block, 64 / LPB consecutive blocks per wave;
-// lane (g, j) holds entries j, j + LPB, ... of block g in registers (EB
-// slots, the wave's bucket), so the reductions are DPP steps inside a quad /
-// half-row and a C2 wave (16 blocks) is ~4 KB of contiguous input: 6250 waves,
-// one resident round at <= 64 VGPRs.
+// Lane mapping: PIPE_LPB = 8 lanes per block, 8 consecutive blocks per wave;
+// lane (g, j) holds entries j, j + 8, ... of block g in registers (PIPE_EB
+// slots), so the reductions are DPP steps inside a half-row.
 template <int CTRL>
 __device__ __forceinline__ int dpp_i(int v) {
     return __builtin_amdgcn_mov_dpp(v, CTRL, 0xF, 0xF, false);
@@ -787,32 +729,25 @@ template <int CTRL>
 __device__ __forceinline__ double dpp_d(double v) {
     return __hiloint2double(dpp_i<CTRL>(__double2hiint(v)), dpp_i<CTRL>(__double2loint(v)));
 }
-// sum / max over the LPB lanes of a group (xor 1, xor 2 in the quad, then the
+// sum / max over the 8 lanes of a group (xor 1, xor 2 in the quad, then the
 // half-row mirror); every lane ends with the same bits (a + b == b + a)
-// (16: then the row mirror, lane i <-> 15 - i, adds the other half-row)
-template <int LPB>
 __device__ __forceinline__ double grp_sum_d(double v) {
-    if constexpr (LPB >= 2) v += dpp_d<0xB1>(v);
-    if constexpr (LPB >= 4) v += dpp_d<0x4E>(v);
-    if constexpr (LPB >= 8) v += dpp_d<0x141>(v);
-    if constexpr (LPB >= 16) v += dpp_d<0x140>(v);
+    v += dpp_d<0xB1>(v);
+    v += dpp_d<0x4E>(v);
+    v += dpp_d<0x141>(v);
     return v;
 }
-template <int LPB>
 __device__ __forceinline__ int grp_sum_i(int v) {
-    if constexpr (LPB >= 2) v += dpp_i<0xB1>(v);
-    if constexpr (LPB >= 4) v += dpp_i<0x4E>(v);
-    if constexpr (LPB >= 8) v += dpp_i<0x141>(v);
-    if constexpr (LPB >= 16) v += dpp_i<0x140>(v);
+    v += dpp_i<0xB1>(v);
+    v += dpp_i<0x4E>(v);
+    v += dpp_i<0x141>(v);
     return v;
 }
-template <int LPB>
 __device__ __forceinline__ double grp_max_d(double v) {
     double u;
-    if constexpr (LPB >= 2) { u = dpp_d<0xB1>(v); v = (u > v) ? u : v; }
-    if constexpr (LPB >= 4) { u = dpp_d<0x4E>(v); v = (u > v) ? u : v; }
-    if constexpr (LPB >= 8) { u = dpp_d<0x141>(v); v = (u > v) ? u : v; }
-    if constexpr (LPB >= 16) { u = dpp_d<0x140>(v); v = (u > v) ? u : v; }
+    u = dpp_d<0xB1>(v); v = (u > v) ? u : v;
+    u = dpp_d<0x4E>(v); v = (u > v) ? u : v;
+    u = dpp_d<0x141>(v); v = (u > v) ? u : v;
     return v;
 }
 
@@ -827,185 +762,32 @@ __device__ __forceinline__ double buf_ld(const __amdgpu_buffer_rsrc_t &rs, int o
     return __builtin_bit_cast(double, __builtin_amdgcn_raw_buffer_load_b64(rs, off, 0, 0));
 }
 
-template <int LPB, int EB, bool BALL>
-__device__ __forceinline__ void thr_solve(int64_t s, int64_t s0, int k, int j,
-                                          const __amdgpu_buffer_rsrc_t &rs) {
-    constexpr double PAD = -1.7976931348623157e308;   // below every entry, finite
-    // every access through the wave's buffer resource: one offset register
-    // (the block's start + j), slot e at + 8 LPB e (folded into the
-    // instruction); ne = this lane's live slots
-    const int base = (int)(s - s0 + j) * 8;
-    const int ne = (k > j) ? (k - j + LPB - 1) / LPB : 0;
-    double v[EB];
-#pragma unroll
-    for (int e = 0; e < EB; ++e) {
-        const double t = buf_ld(rs, base + 8 * LPB * e);   // past the range: 0
-        v[e] = (e < ne) ? t : PAD;
-    }
-    bool need = true;
-    if constexpr (BALL) {
-        // proj_simplex.h:56-64: clamp the negatives, project iff the rest sums > 1
-        double acc = 0.0;
-#pragma unroll
-        for (int e = 0; e < EB; ++e) {
-            const bool ok = e < ne;
-            v[e] = (ok & (v[e] < 0.0)) ? 0.0 : v[e];
-            acc += ok ? v[e] : 0.0;
-        }
-        need = grp_sum_d<LPB>(acc) > 1.0;
-    }
-    double lam = 0.0;
-    if (!BALL || __builtin_amdgcn_ballot_w64(need && k > 0)) {
-        double M = v[0];
-#pragma unroll
-        for (int e = 1; e < EB; ++e) M = (v[e] > M) ? v[e] : M;
-        M = grp_max_d<LPB>(M);
-        // tau stays below the max (clamped to the next double down: only a
-        // |y| ~ 1e12+ rounding could reach it), so the max never leaves the set
-        const double Mdn = next_down(M);
-        double tau = fmin(M - 1.0, Mdn);
-        double cprev = 1.0;   // tau_0 is the tau of the set {max}
-        double S = M, c = 1.0;
-        for (int pass = 0; pass <= LPB * EB; ++pass) {
-            double sl = 0.0, cl = 0.0;
-#pragma unroll
-            for (int e = 0; e < EB; ++e) {
-                // branch-free and mask-free: an entry leaving the set becomes
-                // PAD in v (the sets only shrink, and PAD never passes again);
-                // sum and count by a 0 / 1 factor (fma: one rounding, = the add)
-                const bool keep = v[e] > tau;
-                v[e] = keep ? v[e] : PAD;
-                const double f = keep ? 1.0 : 0.0;
-                sl = __builtin_fma(f, v[e], sl);
-                cl += f;
-            }
-            S = grp_sum_d<LPB>(sl);
-            c = grp_sum_d<LPB>(cl);
-            const bool more = (k > 0) & need & (c != cprev);
-            cprev = c;
-            tau = fmin((S - 1.0) / c, Mdn);
-            if (!__builtin_amdgcn_ballot_w64(more)) break;
-        }
-        lam = (1. - S) / c;
-    }
-    // out: the entries read again (the passes overwrote the dropped ones; the
-    // lines are still in the caches), padding slots' offsets past the end so
-    // the hardware drops their stores (no per-slot branch)
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int e = 0; e < EB; ++e) {
-        double o = buf_ld(rs, base + 8 * LPB * e);
-        if (BALL) o = (o < 0.0) ? 0.0 : o;
-        const double r = need ? relu_ref(lam + o) : o;
-        __builtin_amdgcn_raw_buffer_store_b64(
-            __builtin_bit_cast(HIP_vector_type<unsigned, 2>::Native_vec_, r), rs,
-            (e < ne) ? base + 8 * LPB * e : 0x7FFFFFF0, 0, 0);
-    }
-}
-
-// One wave: blocks b0 .. b0 + 64/LPB - 1 (block ends from the same coalesced
-// read of starts); blocks > SMALL_MAX go to the big list as in lds_group.
-// at least BSLS_PROJ_MINW waves per SIMD (<= 512 / MINW VGPRs): the C2 grid
-// (6250 waves at LPB 4) must be resident in one round -- at 73 VGPRs (six
-// waves per SIMD, 6144 slots) 106 waves ran as a second round
-#ifndef BSLS_PROJ_MINW
-#define BSLS_PROJ_MINW 8
-#endif
-template <bool BALL, int LPB>
-__global__ __launch_bounds__(256, BSLS_PROJ_MINW) void proj_thr_kernel(double *__restrict__ y,
-                                                      const int64_t *__restrict__ starts,
-                                                      int64_t nb, int64_t n,
-                                                      int64_t *__restrict__ big_list,
-                                                      unsigned *__restrict__ big_count,
-                                                      int allow_big,
-                                                      const double *__restrict__ gate) {
-    static_assert(LPB == 2 || LPB == 4 || LPB == 8, "lanes per block");
-    constexpr int BPW = WAVE / LPB;
-    if (gate && *gate != 1.0) return;
-    const int lane = lane_id();
-    const int64_t wave = (int64_t)blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE;
-    const int64_t b0 = wave * BPW;
-    if (b0 >= nb) return;
-    const int g = lane / LPB, j = lane % LPB;
-    long long st = (long long)n;
-    if (lane <= BPW && b0 + lane < nb) st = (long long)starts[b0 + lane];
-    const int64_t s = (int64_t)__shfl(st, g, WAVE);
-    const int64_t e = (int64_t)__shfl(st, g + 1, WAVE);
-    const int64_t b = b0 + g;
-    int k = 0;
-    if (b < nb) {
-        const int64_t kk = e - s;
-        if (kk > SMALL_MAX) {
-            if (allow_big && j == 0) {   // (a block > max_block breaks the contract: left as is)
-                const unsigned slot = atomicAdd(big_count, 1u);
-                big_list[slot] = b;
-            }
-        } else {
-            k = (int)kk;
-        }
-    }
-    const int kmax = wave_max(k);
-    if (kmax == 0) return;
-    // the wave's range [s0, e1): its first block's start to its last block's end
-    // (read into scalar registers: a buffer resource built from VGPRs becomes
-    // a waterfall loop around every store)
-    const int64_t s0 = uni64((int64_t)st, 0);
-    const int nbw = __builtin_amdgcn_readfirstlane((int)((nb - b0 < BPW) ? nb - b0 : BPW));
-    const int64_t e1 = uni64((int64_t)st, nbw);
-    const __amdgpu_buffer_rsrc_t rs =
-        __builtin_amdgcn_make_buffer_rsrc(y + s0, 0, (int)((e1 - s0) * 8), 0x00020000);
-    const int E = (kmax + LPB - 1) / LPB;
-    if (E <= 4) thr_solve<LPB, 4, BALL>(s, s0, k, j, rs);
-    else if (E <= 8) thr_solve<LPB, 8, BALL>(s, s0, k, j, rs);
-    else if constexpr (LPB <= 4) {
-        if (E <= 12) thr_solve<LPB, 12, BALL>(s, s0, k, j, rs);
-        else if (E <= 16) thr_solve<LPB, 16, BALL>(s, s0, k, j, rs);
-        else if constexpr (LPB == 2) {
-            if (E <= 24) thr_solve<LPB, 24, BALL>(s, s0, k, j, rs);
-            else thr_solve<LPB, 32, BALL>(s, s0, k, j, rs);
-        }
-    }
-}
-
-// ---- the pipelined sort-free kernel (the default fast form, round 5) --------
+// ---- the group kernel (the fast form, round 5) ------------------------------
 //
-// The lane-per-block kernels above load, compute and store in lockstep: C2's
+// The lane-per-block kernel above loads, computes and stores in lockstep: C2's
 // 100k blocks make 1563 waves, ~1.5 per SIMD, each one long serial chain, so
 // nothing overlaps the memory phases (with the compute knocked out the exact
 // kernel still takes ~14 us to stream C2, a copy 8).  Here a block gets
 // PIPE_LPB = 8 lanes (entry j + 8 e of the block in slot e of its lane j,
 // PIPE_EB = 8 slots: blocks of <= 64; longer ones go to the big list as in
-// lds_group), a GROUP of 8 consecutive blocks is one wave's unit, and a
-// persistent wave walks groups w, w + W, w + 2 W, ... with the next group's
-// entries and the block starts of the group after it already in flight while
-// it runs Michelot's passes on the current group and stores it: every wave
-// keeps loads outstanding through its compute, so HBM stays busy.  A load
-// instruction reads 8 runs of 8 consecutive doubles (one per block), a store
-// writes them back from registers: no LDS, ~60 VGPRs.
+// lds_group) and a GROUP of 8 consecutive blocks is one wave's unit: 8 times
+// the waves, each a short chain, so the chip has many more bytes in flight.
 //
 // Per pass a lane tests its 8 slots against tau, and the block's sum and
 // count of {v > tau} come from three DPP steps inside the 8-lane group
 // (grp_sum_*: every lane of the group ends with the same bits).  tau starts
 // at max(M - 1, (S - 1) / k) -- the thresholds of the sets {max} and of the
-// whole block, both lower bounds of the projection's (thr_solve's comment) --
+// whole block, both lower bounds of the projection's (any subset's is one) --
 // so U[0,1) blocks of ~32 take ~3-4 passes and 5 N(0,1) blocks 1-2.  The
 // entries stay unchanged in registers (tau only grows, so {v > tau} shrinks
 // by itself) and the output is relu(lambda + v) from them: lambda = (1 -
 // S) / c, the reference's expression at rho = c - 1 with its members summed
-// in another order (1e-12 contract, as thr_solve).
-#ifndef BSLS_PIPE_LPB
-#define BSLS_PIPE_LPB 8   // lanes per block (4, 8 or 16; A/B variant builds)
-#endif
-#ifndef BSLS_PIPE_STORE_AUX
-#define BSLS_PIPE_STORE_AUX 16   // the stores' cache policy: sc1 (write-through); 0 plain
-#endif
-#ifndef BSLS_PIPE_LDS_TRIM
-#define BSLS_PIPE_LDS_TRIM 0   // 1: the LDS variant skips its loads past the group's range
-#endif
+// in another order (the 1e-12 contract).
 #ifndef BSLS_PIPE_KO
 #define BSLS_PIPE_KO 0    // 1: no threshold passes (knock-out timing build, results wrong)
 #endif
-constexpr int PIPE_LPB = BSLS_PIPE_LPB, PIPE_EB = 64 / PIPE_LPB, PIPE_BPG = WAVE / PIPE_LPB;
+constexpr int PIPE_LPB = 8, PIPE_EB = 64 / PIPE_LPB, PIPE_BPG = WAVE / PIPE_LPB;
+constexpr int PIPE_STORE_AUX = 16;   // the stores' cache policy: sc1 (write-through)
 
 struct PipeGroup {
     __amdgpu_buffer_rsrc_t rs;   // the group's range [s0, e1) of y (scalar registers)
@@ -1086,7 +868,7 @@ __device__ __forceinline__ PipeOut pipe_threshold(int k, double (&v)[PIPE_EB], i
         S += ok ? v[e] : 0.0;
         v[e] = ok ? v[e] : PAD;
     }
-    S = grp_sum_d<PIPE_LPB>(S);
+    S = grp_sum_d(S);
     const bool need = !BALL || S > 1.0;
     // the slots any lane of the wave holds (wave-uniform: past them every
     // slot is padding, skipped by a scalar branch instead of computed)
@@ -1102,9 +884,9 @@ __device__ __forceinline__ PipeOut pipe_threshold(int k, double (&v)[PIPE_EB], i
         // a third lower bound: the threshold of the set of the lanes' maxima
         // (min(k, LPB) members -- any subset's threshold is one).  U[0,1)
         // blocks of ~32: ~0.68 where the whole block's is ~0.47, one pass less
-        const double SL = grp_sum_d<PIPE_LPB>(ne > 0 ? M : 0.0);
+        const double SL = grp_sum_d(ne > 0 ? M : 0.0);
         const double kl = (double)(k < PIPE_LPB ? k : PIPE_LPB);
-        M = grp_max_d<PIPE_LPB>(M);
+        M = grp_max_d(M);
         // tau stays below the max (clamped to the next double down: only a
         // |y| ~ 1e12+ rounding could reach it), so the max never leaves the set
         const double Mdn = next_down(M);
@@ -1130,8 +912,8 @@ __device__ __forceinline__ PipeOut pipe_threshold(int k, double (&v)[PIPE_EB], i
                 sl = __builtin_fma(f, v[e], sl);
                 cl += f;
             }
-            S = grp_sum_d<PIPE_LPB>(sl);
-            c = grp_sum_d<PIPE_LPB>(cl);
+            S = grp_sum_d(sl);
+            c = grp_sum_d(cl);
             const bool more = (k > 0) & need & (c != cprev);
             cprev = c;
             tau = fmin((S - 1.0) / c, Mdn);
@@ -1158,76 +940,31 @@ __device__ __forceinline__ void pipe_solve(const PipeGroup &G, double (&v)[PIPE_
         const double r = need ? relu_ref(lam + v[e]) : v[e];
         __builtin_amdgcn_raw_buffer_store_b64(
             __builtin_bit_cast(HIP_vector_type<unsigned, 2>::Native_vec_, r), G.rs,
-            (e < ne) ? G.base + 8 * PIPE_LPB * e : 0x7FFFFFF0, 0, BSLS_PIPE_STORE_AUX);
+            (e < ne) ? G.base + 8 * PIPE_LPB * e : 0x7FFFFFF0, 0, PIPE_STORE_AUX);
     }
 }
 
-// One wave: PIPE_G consecutive groups, straight-line (unrolled at compile
-// time): the starts of all of them in one load, then the entries of every
-// group, then the passes and stores group by group -- so a wave has all its
-// bytes in flight at once and computes on the first group while the others
-// land (round 5, measured at C2: one group ahead per step was slower than no
-// pipelining at all, 23.9 against 19.1 us -- what the kernel is short of is
-// bytes in flight per CU, not overlap inside a wave).  Straight-line code keeps
-// the compiler's vmcnt waits exact; every memory operation is unconditional:
-// a group past the last is a clamped copy with k = 0, whose stores the
-// hardware drops.
-template <bool BALL, bool BIG, int PIPE_G>
-__global__ __launch_bounds__(256, 2) void proj_pipe_kernel(double *__restrict__ y,
-                                                          const int64_t *__restrict__ starts,
-                                                          int64_t nb, int64_t n,
-                                                          int64_t *__restrict__ big_list,
-                                                          unsigned *__restrict__ big_count,
-                                                          const double *__restrict__ gate) {
-    if (gate && *gate != 1.0) return;
-    const int lane = lane_id(), j = lane % PIPE_LPB;
-    const int64_t ngrp = (nb + PIPE_BPG - 1) / PIPE_BPG;
-    const int64_t q0 = (int64_t)__builtin_amdgcn_readfirstlane(
-                           (int)(blockIdx.x * (blockDim.x / WAVE) + threadIdx.x / WAVE)) * PIPE_G;
-    if (q0 >= ngrp) return;
-    long long st[PIPE_G];
-#pragma unroll
-    for (int h = 0; h < PIPE_G; ++h)
-        st[h] = pipe_meta(starts, nb, n, (q0 + h < ngrp) ? q0 + h : ngrp - 1, lane);
-    asm volatile("" ::: "memory");
-    PipeGroup P[PIPE_G];
-    double v[PIPE_G][PIPE_EB];
-#pragma unroll
-    for (int h = 0; h < PIPE_G; ++h) {
-        const int64_t q = q0 + h;
-        const bool real = q < ngrp;
-        P[h] = pipe_setup<BIG>(y, st[h], real ? q : ngrp - 1, nb, big_list, big_count, real, lane);
-        if (!real) P[h].k = 0;
-        pipe_load(P[h], v[h]);
-    }
-    // (keeps the compiler from sinking those loads past the passes)
-    asm volatile("" ::: "memory");
-#pragma unroll
-    for (int h = 0; h < PIPE_G; ++h) pipe_solve<BALL>(P[h], v[h], j);
-}
-
-// The same group through LDS (round 5 A/B, BSLS_PROJ_PIPE_LDS): the group's
+// The group through LDS (proj_pipe_lds_kernel, the fast form): the group's
 // range [s0, e1) comes in by 8-B coalesced loads (lane l, load e: entry 64 e +
 // l -- 512 contiguous bytes per wave instruction, where the block-aligned
-// loads read 8 runs of 64 B), goes to the lanes' block slots through the
-// wave's own 4-KB LDS buffer, and back out the same way (write-through).  A
-// group longer than PIPE_STAGE entries (big blocks inside) takes the direct
-// path.  Entries of big blocks inside the range go back unchanged (the big-
-// block kernel that follows in the stream projects them).
+// loads of pipe_load read 8 runs of 64 B), goes to the lanes' block slots
+// through the wave's own 4.5-KB LDS buffer, and back out the same way
+// (write-through): C2 17.1 against 20.5 us for the removed direct kernel,
+// which took every group straight into the lanes' registers (round 5, HBM-fed
+// batch).  A group longer than PIPE_STAGE entries (big blocks inside) still
+// goes that way (pipe_group_one).  Entries of big blocks inside the range go
+// back unchanged (the big-block kernel that follows in the stream projects
+// them).
 // PIPE_STAGE: the LDS buffer's entries per wave (a group's range up to it
-// goes through LDS); BSLS_PIPE_STAGE overrides it for the A/B builds
-#ifndef BSLS_PIPE_STAGE
-#define BSLS_PIPE_STAGE (PIPE_BPG * 64)
-#endif
-constexpr int PIPE_STAGE = BSLS_PIPE_STAGE, PIPE_NL = PIPE_STAGE / WAVE;
+// goes through LDS)
+constexpr int PIPE_STAGE = PIPE_BPG * 64, PIPE_NL = PIPE_STAGE / WAVE;
 static_assert(PIPE_STAGE % WAVE == 0, "the LDS stage is whole wave rows");
 
 // the group's range by coalesced 8-B loads (lane l, load e: entry 64 e + l;
 // past the range the hardware returns 0)
 __device__ __forceinline__ void lds_range_load(const PipeGroup &G, double (&t)[PIPE_NL], int lane) {
 #pragma unroll
-    for (int e = 0; e < PIPE_NL; ++e)
-        t[e] = (BSLS_PIPE_LDS_TRIM && WAVE * e >= G.len) ? 0.0 : buf_ld(G.rs, (WAVE * e + lane) * 8);
+    for (int e = 0; e < PIPE_NL; ++e) t[e] = buf_ld(G.rs, (WAVE * e + lane) * 8);
 }
 
 // t to the wave's LDS buffer, the lanes' block slots out of it, Michelot,
@@ -1252,7 +989,7 @@ __device__ __forceinline__ void lds_group(const PipeGroup &G, const double (&t)[
         const int i = WAVE * e + lane;
         __builtin_amdgcn_raw_buffer_store_b64(
             __builtin_bit_cast(HIP_vector_type<unsigned, 2>::Native_vec_, buf[i]), G.rs,
-            i < G.len ? i * 8 : 0x7FFFFFF0, 0, BSLS_PIPE_STORE_AUX);
+            i < G.len ? i * 8 : 0x7FFFFFF0, 0, PIPE_STORE_AUX);
     }
 }
 
@@ -1271,14 +1008,7 @@ __device__ __forceinline__ void pipe_group_one(const PipeGroup &G, double *buf, 
     lds_group<BALL>(G, t, buf, lane, j);
 }
 
-// The same group through LDS (round 5, the default fast form; BSLS_PROJ_PIPE_LDS):
-// the group's range [s0, e1) comes in by 8-B coalesced loads (512 contiguous
-// bytes per wave instruction, where the block-aligned loads read 8 runs of
-// 64 B), goes to the lanes' block slots through the wave's own LDS buffer,
-// and back out the same way (write-through).  A group longer than
-// PIPE_STAGE entries (big blocks inside) takes the direct path.  Entries of
-// big blocks inside the range go back unchanged (the big-block kernel that
-// follows in the stream projects them).
+// One wave per group, four waves per workgroup, each with its own LDS stage.
 template <bool BALL, bool BIG>
 __global__ __launch_bounds__(256, 2) void proj_pipe_lds_kernel(double *__restrict__ y,
                                                               const int64_t *__restrict__ starts,
@@ -1348,92 +1078,27 @@ static int proj_launch(double *y, const int64_t *starts, int64_t nb, int64_t n,
     // the big-block list is only used when some block can exceed SMALL_MAX
     // (max_block is the caller's bound on every block length, like the
     // workspace size derived from it): otherwise no reset launch at all
-    if (max_block > SMALL_MAX) BSLS_CHECK(hipMemsetAsync(w.count, 0, 16, st));
-    // waves per workgroup (BSLS_PROJ_WAVES, A/B): 2, staggered, by default --
-    // C2 20.7 -> 20.2 us per launch (HBM-fed batch); 3 is slower (27.9 us:
-    // 60 KB of LDS per workgroup leave 512 slots for 521 workgroups, a tail)
-    static const int pw = [] {
-        const char *e = getenv("BSLS_PROJ_WAVES");
-        const int v = e ? atoi(e) : 2;
-        return (v == 1 || v == 3) ? v : 2;
-    }();
-    // the sort-free path: one lane per block (Michelot on the staged block,
-    // proj_lds_kernel<BALL, 2, true>) unless BSLS_PROJ_LPB (A/B) asks for
-    // proj_thr_kernel's 2 / 4 / 8 lanes per block
-    static const int lpb = [] {
-        const char *e = getenv("BSLS_PROJ_LPB");
-        const int v = e ? atoi(e) : 0;
-        return (v == 2 || v == 4 || v == 8) ? v : 0;
-    }();
-    // the pipelined kernel's groups per wave (BSLS_PROJ_PIPE = 1, 2, 4 or 8,
-    // A/B; 0 = the lane-per-block Michelot form below)
-    static const int pipe = [] {
-        const char *e = getenv("BSLS_PROJ_PIPE");
-        const int v = e ? atoi(e) : 1;
-        return (v == 0 || v == 1 || v == 2 || v == 4 || v == 8) ? v : 1;
-    }();
-    const int64_t ngrp = (nb + WAVE - 1) / WAVE;
-    // (its group ranges must stay below 2 GB of y: max_block bounds them)
-    if (fast && lpb == 0 && pipe > 0 && max_block <= ((int64_t)1 << 24)) {
+    const bool big = max_block > SMALL_MAX;
+    if (big) BSLS_CHECK(hipMemsetAsync(w.count, 0, 16, st));
+    // the fast contract's group kernel while its group ranges stay below 2 GB
+    // of y (max_block bounds them); a larger bound takes the exact launch,
+    // whose bit-identical output meets the fast contract too
+    if (fast && max_block <= ((int64_t)1 << 24)) {
         const int64_t groups = (nb + PIPE_BPG - 1) / PIPE_BPG;
-        const int64_t waves = (groups + pipe - 1) / pipe;
-        const unsigned grid = (unsigned)((waves + 3) / 4);
-        const bool big = max_block > SMALL_MAX;
-#define BSLS_PIPE_LAUNCH(G)                                                                     \
-    do {                                                                                        \
-        if (big)                                                                                \
-            proj_pipe_kernel<BALL, true, G><<<grid, 256, 0, st>>>(y, starts, nb, n, w.list,     \
-                                                                  w.count, gate);               \
-        else                                                                                    \
-            proj_pipe_kernel<BALL, false, G><<<grid, 256, 0, st>>>(y, starts, nb, n, w.list,    \
-                                                                   w.count, gate);              \
-    } while (0)
-        // through LDS (coalesced in and out) by default: C2 17.1 against 20.5
-        // us for the direct form (round 5, HBM-fed batch); BSLS_PROJ_PIPE_LDS=0
-        // selects the direct form (A/B)
-        static const int via_lds = [] {
-            const char *e = getenv("BSLS_PROJ_PIPE_LDS");
-            return e ? atoi(e) : 1;
-        }();
-        if (via_lds) {
-            const unsigned g1 = (unsigned)((groups + 3) / 4);
-            if (big)
-                proj_pipe_lds_kernel<BALL, true><<<g1, 256, 0, st>>>(y, starts, nb, n, w.list,
-                                                                     w.count, gate);
-            else
-                proj_pipe_lds_kernel<BALL, false><<<g1, 256, 0, st>>>(y, starts, nb, n, w.list,
-                                                                      w.count, gate);
-        } else if (pipe == 1) BSLS_PIPE_LAUNCH(1);
-        else if (pipe == 2) BSLS_PIPE_LAUNCH(2);
-        else if (pipe == 8) BSLS_PIPE_LAUNCH(8);
-        else BSLS_PIPE_LAUNCH(4);
-#undef BSLS_PIPE_LAUNCH
-    } else if (fast && lpb == 0) {
-        proj_lds_kernel<BALL, 2, true><<<(unsigned)((ngrp + 1) / 2), 2 * WAVE, 0, st>>>(
-            y, starts, nb, n, w.list, w.count, max_block > SMALL_MAX, gate);
-    } else if (fast) {
-        const int64_t waves = (nb + WAVE / lpb - 1) / (WAVE / lpb);
-        const unsigned grid = (unsigned)((waves + 3) / 4);
-        if (lpb == 2)
-            proj_thr_kernel<BALL, 2><<<grid, 256, 0, st>>>(y, starts, nb, n, w.list, w.count,
-                                                          max_block > SMALL_MAX, gate);
-        else if (lpb == 8)
-            proj_thr_kernel<BALL, 8><<<grid, 256, 0, st>>>(y, starts, nb, n, w.list, w.count,
-                                                          max_block > SMALL_MAX, gate);
+        const unsigned grid = (unsigned)((groups + 3) / 4);
+        if (big)
+            proj_pipe_lds_kernel<BALL, true><<<grid, 256, 0, st>>>(y, starts, nb, n, w.list,
+                                                                   w.count, gate);
         else
-            proj_thr_kernel<BALL, 4><<<grid, 256, 0, st>>>(y, starts, nb, n, w.list, w.count,
-                                                          max_block > SMALL_MAX, gate);
-    } else if (pw == 3)
-        proj_lds_kernel<BALL, 3><<<(unsigned)((ngrp + 2) / 3), 3 * WAVE, 0, st>>>(
-            y, starts, nb, n, w.list, w.count, max_block > SMALL_MAX, gate);
-    else if (pw == 2)
-        proj_lds_kernel<BALL, 2><<<(unsigned)((ngrp + 1) / 2), 2 * WAVE, 0, st>>>(
-            y, starts, nb, n, w.list, w.count, max_block > SMALL_MAX, gate);
-    else
-        proj_lds_kernel<BALL, 1><<<grid_for(nb, WAVE), WAVE, 0, st>>>(
-            y, starts, nb, n, w.list, w.count, max_block > SMALL_MAX, gate);
+            proj_pipe_lds_kernel<BALL, false><<<grid, 256, 0, st>>>(y, starts, nb, n, w.list,
+                                                                    w.count, gate);
+    } else {
+        const int64_t ngrp = (nb + WAVE - 1) / WAVE;
+        proj_lds_kernel<BALL><<<(unsigned)((ngrp + LDS_WAVES - 1) / LDS_WAVES), LDS_WAVES * WAVE, 0,
+                                st>>>(y, starts, nb, n, w.list, w.count, big, gate);
+    }
     BSLS_LAUNCH_CHECK();
-    if (max_block > SMALL_MAX) {
+    if (big) {
         int64_t nbig = nb < (n / (SMALL_MAX + 1) + 1) ? nb : (n / (SMALL_MAX + 1) + 1);
         int grid = (int)(nbig < 2048 ? nbig : 2048);
         const size_t lds = (SCRATCH_WORDS + 2 * LDS_MAX) * sizeof(double);

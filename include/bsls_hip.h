@@ -53,7 +53,8 @@ int bsls_proj_multi_ball(double *d_y, const int64_t *d_starts, int64_t nblocks, 
  * nothing has the reference's set, proj_simplex.h:27-31), the set's sum in a
  * fixed lane order instead of the sorted prefix chain.  Within 1e-12 *
  * max(1, |reference|) of the reference on every tested input (the north
- * star's projection contract), deterministic, not bit-identical. */
+ * star's projection contract), deterministic, not bit-identical.  A max_block
+ * above 2^24 takes the bit-identical path of the two calls above. */
 int bsls_proj_multi_simplex_fast(double *d_y, const int64_t *d_starts, int64_t nblocks, int64_t n,
                                  int64_t max_block, void *d_work, size_t work_bytes, void *stream);
 int bsls_proj_multi_ball_fast(double *d_y, const int64_t *d_starts, int64_t nblocks, int64_t n,

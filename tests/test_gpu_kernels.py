@@ -137,15 +137,14 @@ def test_proj_borderline_decisions(cx, orc, exact_proj):
 
 
 def test_proj_exact_pipe_verification_fallbacks(cx, orc, exact_proj):
-    """The pipelined exact path (csrc/proj.hip pipe_exact_lambda) verifies
-    Michelot's candidate set in the reference's arithmetic and redoes a block
-    the reference's way where it cannot: blocks whose threshold lands exactly
+    """Boundary inputs of the exact path: blocks whose threshold lands exactly
     on an entry (0.75, 0.25, 0, ...: e_c = 0 at the boundary), ties across
     the boundary, all-equal blocks (every entry a member), single entries;
     ball blocks whose clamped sum is 1 to within a few ulps (the left-to-right
     sum decides, proj_simplex.h:56-66); mixed with blocks > 64 inside a wave's
     range (their entries must come back untouched for the big-block kernel).
-    Bit-identical to the oracle."""
+    Bit-identical to the oracle.  (Written for a pipelined exact kernel that
+    was reverted; the inputs stay as a test of the sorting kernel.)"""
     rs = np.random.RandomState(SEED + 11)
     blocks = []
     for _ in range(400):
@@ -334,6 +333,18 @@ def test_fast_proj_c_abi_entry(cuda, orc):
         out = yd.cpu().numpy()
         assert close12(out, r)
         assert out[0] == y[0] and out[1] == y[1]      # before the first block: untouched
+        # a bound past the group kernel's range limit (2^24; max_block is only
+        # the caller's bound) takes the bit-identical launch; the huge-path
+        # launches the bound enables find no block of their size
+        mb_far = (1 << 24) + 1
+        yd = torch.from_numpy(y).cuda()
+        ws_far = torch.zeros(L.bsls_proj_workspace_size(n, sizes.size, mb_far), dtype=torch.uint8,
+                             device='cuda')
+        check(fn(ptr(yd), ptr(sd), sizes.size, n, mb_far, ptr(ws_far), ws_far.numel(),
+                 stream_handle()), 'fast, max_block > 2^24')
+        out = yd.cpu().numpy()
+        assert exact(out, r)
+        assert out[0] == y[0] and out[1] == y[1]
     assert L.bsls_proj_multi_simplex_fast(None, None, 0, 0, 1, None, 0, None) == _native.BSLS_E_ARG
 
 
