@@ -272,25 +272,44 @@ __device__ __forceinline__ void k1_stopped_rows(const bsls_bb_problem &P, int64_
     for (int64_t row = r0 + t0; row < r1; row += stride) P.r[row] = 0.0;
 }
 
+// bsls_bb_problem.roww, a row's value o under its weight w: what r stores (an
+// exact +0.0 for a held-out row, w == 0, whatever o is -- selected out, not
+// multiplied, so a NaN or inf there reaches `held` only), its share w o^2 of
+// the objective into sq and, held out, o^2 into held.
+__device__ __forceinline__ double k1_weigh(double o, double w, double &sq, double &held) {
+    const bool out = (w == 0.0);
+    const double wo = out ? 0.0 : w * o;
+    sq += out ? 0.0 : o * wo;
+    held += out ? o * o : 0.0;
+    return wo;
+}
+
 // K1's finish for row block rb (rows [r0, r1)), run by one workgroup: r =
 // the G partials of each row summed in group order (from rpart, or from LDS
 // `local` when the block had one group) + target; its share of ||r||^2 goes
 // to the last row block, which records f and runs the stopping test.
 // FX (fx_sums): |r| of the rows folded into rmax for the next K2's scale.
-template <bool ADD, bool REDUCE, bool FX = false>
+// RW (bsls_bb_problem.roww): the weighted finish, k1_weigh.
+template <bool ADD, bool REDUCE, bool FX = false, bool RW = false>
 __device__ __forceinline__ void k1_finish(const bsls_bb_problem &P, int64_t iter, bool iterating,
                                           int64_t rb, unsigned nrb, int64_t r0, int64_t r1,
                                           int64_t G, const double *local, double *part,
                                           unsigned *ticket, double *red,
                                           unsigned long long *rmax = nullptr) {
-    double sq[1] = {0.0};
+    static_assert(!RW || (ADD && !FX), "weights: the finishes that add target, float sums");
+    constexpr int NS = RW ? 2 : 1;   // (RW: [1] the held-out rows' o^2)
+    double sq[NS] = {};
     unsigned long long mb = 0ull;
     if (local) {
         for (int64_t row = r0 + threadIdx.x; row < r1; row += blockDim.x) {
             double o = local[row - r0];
             if (ADD) o += P.target[row];
-            P.r[row] = o;
-            sq[0] += o * o;
+            if constexpr (RW) {
+                P.r[row] = k1_weigh(o, P.roww[row], sq[0], sq[NS - 1]);
+            } else {
+                P.r[row] = o;
+                sq[0] += o * o;
+            }
             if constexpr (FX) mb = umax64(mb, abs_bits(o));
         }
     } else {
@@ -320,18 +339,24 @@ __device__ __forceinline__ void k1_finish(const bsls_bb_problem &P, int64_t iter
                     o += __hip_atomic_load(&P.rpart[c * P.m + row], __ATOMIC_RELAXED,
                                            __HIP_MEMORY_SCOPE_AGENT);
                 if (ADD) o += P.target[row];
-                P.r[row] = o;
-                sq[0] += o * o;
+                if constexpr (RW) {
+                    P.r[row] = k1_weigh(o, P.roww[row], sq[0], sq[NS - 1]);
+                } else {
+                    P.r[row] = o;
+                    sq[0] += o * o;
+                }
                 if constexpr (FX) mb = umax64(mb, abs_bits(o));
             }
         }
     }
     if constexpr (FX) rmax_fold(rmax, mb);
     if (!REDUCE) return;
-    block_sum<1>(sq, red);
-    double tot[1];
-    if (last_of_sum<1>(sq, part, (unsigned)rb, nrb, ticket, tot, red) && threadIdx.x == 0)
+    block_sum<NS>(sq, red);
+    double tot[NS];
+    if (last_of_sum<NS>(sq, part, (unsigned)rb, nrb, ticket, tot, red) && threadIdx.x == 0) {
+        if constexpr (RW) P.scal[BSLS_S_HELD] = tot[NS - 1];
         bb_record_f(P, iter, tot[0], iterating);
+    }
 }
 
 // K1: workgroup (group g = blockIdx % ngroups, panels 16 rb .. 16 rb + 15)
@@ -340,7 +365,7 @@ __device__ __forceinline__ void k1_finish(const bsls_bb_problem &P, int64_t iter
 // The last of the row block's ngroups workgroups to arrive sums the partials
 // in group order (+ target), writes r, and (REDUCE) hands its share of
 // ||r||^2 to the last row block, which records f and runs the stopping test.
-template <int MODE, bool ITER, bool ADD, bool REDUCE>
+template <int MODE, bool ITER, bool ADD, bool REDUCE, bool RW = false>
 __global__ __launch_bounds__(1024) void bb_k1(bsls_bb_problem P, int64_t iter, unsigned *tkrb,
                                               double *part, unsigned *ticket, int64_t rb_base) {
     extern __shared__ __attribute__((aligned(16))) double lds[];
@@ -377,7 +402,8 @@ __global__ __launch_bounds__(1024) void bb_k1(bsls_bb_problem P, int64_t iter, u
     const int64_t r0 = rb * PANEL_WAVES * M.prow;
     const int64_t r1 = (r0 + PANEL_WAVES * M.prow < P.m) ? r0 + PANEL_WAVES * M.prow : P.m;
     const unsigned nrb = (unsigned)((M.npanels + PANEL_WAVES - 1) / PANEL_WAVES);
-    k1_finish<ADD, REDUCE>(P, iter, ITER, rb, nrb, r0, r1, G, nullptr, part, ticket, lds);
+    k1_finish<ADD, REDUCE, false, RW>(P, iter, ITER, rb, nrb, r0, r1, G, nullptr, part, ticket,
+                                      lds);
 }
 
 // A K1 tile launch with several column groups ends once its partials are
@@ -411,14 +437,25 @@ __device__ __forceinline__ unsigned long long k1_abs(bb_d2 o) {
     return umax64(abs_bits(o.x), abs_bits(o.y));
 }
 
+__device__ __forceinline__ bb_d2 k1_weigh(bb_d2 o, bb_d2 w, double &sq, double &held) {
+    bb_d2 wo;
+    wo.x = k1_weigh(o.x, w.x, sq, held);
+    wo.y = k1_weigh(o.y, w.y, sq, held);
+    return wo;
+}
+
 // FX (fx_sums): |r| of the rows folded into rmax, as k1_finish
-template <bool ITER, bool ADD, bool REDUCE, int W = 1, bool FX = false>
+// RW (roww): the weighted finish, as k1_finish (W = 2: the pair's weights as
+// one 16-B load beside target's)
+template <bool ITER, bool ADD, bool REDUCE, int W = 1, bool FX = false, bool RW = false>
 __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter, int64_t G,
                                                  int64_t r0, int64_t r1, double *part,
                                                  unsigned *ticket,
                                                  unsigned long long *rmax = nullptr) {
+    static_assert(!RW || (ADD && !FX), "weights: the finishes that add target, float sums");
+    constexpr int NS = RW ? 2 : 1;   // (RW: [1] the held-out rows' o^2)
     typedef typename K1SumVec<W>::type vec;
-    __shared__ double red[8];
+    __shared__ double red[8];   // (NS doubles per wave)
     PH_DECL;
     PH(0);
     const double stop = ITER ? P.scal[BSLS_S_STOP] : 0.0;
@@ -430,12 +467,14 @@ __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter
     int64_t idx = t0;
     const int64_t ni = (r1 - r0) / W;   // whole items (>= 1)
     vec v[8], tg;
+    [[maybe_unused]] vec wt;
     auto load = [&](int64_t i) {
         const int64_t row = r0 + W * (i < ni ? i : ni - 1);
 #pragma unroll
         for (int c = 0; c < 8; ++c)
             v[c] = (c < G) ? *reinterpret_cast<const vec *>(&P.rpart[c * P.m + row]) : vec{};
         tg = ADD ? *reinterpret_cast<const vec *>(&P.target[row]) : vec{};
+        if constexpr (RW) wt = *reinterpret_cast<const vec *>(&P.roww[row]);
     };
     load(idx);
     if (ITER && stop != 0.0) {
@@ -443,7 +482,7 @@ __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter
         return;
     }
     PH(1);
-    double sq[1] = {0.0};
+    double sq[NS] = {};
     unsigned long long mb = 0ull;
     while (idx < ni) {
         const int64_t row = r0 + W * idx;
@@ -453,8 +492,12 @@ __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter
             if (c < G) o += v[c];
         for (int64_t c = 8; c < G; ++c) o += *reinterpret_cast<const vec *>(&P.rpart[c * P.m + row]);
         if (ADD) o += tg;
-        *reinterpret_cast<vec *>(&P.r[row]) = o;
-        sq[0] += k1_sq(o);
+        if constexpr (RW) {
+            *reinterpret_cast<vec *>(&P.r[row]) = k1_weigh(o, wt, sq[0], sq[NS - 1]);
+        } else {
+            *reinterpret_cast<vec *>(&P.r[row]) = o;
+            sq[0] += k1_sq(o);
+        }
         if constexpr (FX) mb = umax64(mb, k1_abs(o));
         idx += gs;
         if (idx < ni) load(idx);
@@ -464,8 +507,12 @@ __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter
         double o = P.rpart[row];
         for (int64_t c = 1; c < G; ++c) o += P.rpart[c * P.m + row];
         if (ADD) o += P.target[row];
-        P.r[row] = o;
-        sq[0] += o * o;
+        if constexpr (RW) {
+            P.r[row] = k1_weigh(o, P.roww[row], sq[0], sq[NS - 1]);
+        } else {
+            P.r[row] = o;
+            sq[0] += o * o;
+        }
         if constexpr (FX) mb = umax64(mb, abs_bits(o));
     }
     PH(2);
@@ -474,10 +521,12 @@ __global__ __launch_bounds__(256) void bb_k1_sum(bsls_bb_problem P, int64_t iter
         PH_FLUSH(PH_SUM);
         return;
     }
-    block_sum<1>(sq, red);
-    double tot[1];
-    if (last_block_sum<1>(sq, part, ticket, tot, red) && threadIdx.x == 0)
+    block_sum<NS>(sq, red);
+    double tot[NS];
+    if (last_block_sum<NS>(sq, part, ticket, tot, red) && threadIdx.x == 0) {
+        if constexpr (RW) P.scal[BSLS_S_HELD] = tot[NS - 1];
         bb_record_f(P, iter, tot[0], ITER);
+    }
     PH(3);
     PH_FLUSH(PH_SUM);
 }
@@ -512,7 +561,10 @@ __global__ __launch_bounds__(256) void bb_k1_init(bsls_bb_problem P, int64_t r0,
 // the caller's bound fx_a1 * x_bound; each row is converted once after the
 // walk, and what follows -- the finish, or the partials and bb_k1_sum -- is the
 // float form's, already ordered.
-template <int MODE, bool ITER, bool ADD, bool REDUCE, bool ATOM = false, bool FX = false>
+// RW (roww, never ATOM or FX): the one-group finish weighted, as k1_finish;
+// with several groups the kernel is RW = false's and bb_k1_sum weighs.
+template <int MODE, bool ITER, bool ADD, bool REDUCE, bool ATOM = false, bool FX = false,
+          bool RW = false>
 __global__ __launch_bounds__(1024, 1) void bb_k1t(bsls_bb_problem P, int64_t iter, double *part,
                                                   unsigned *ticket, int64_t rb_base,
                                                   unsigned long long *rmax = nullptr) {
@@ -560,8 +612,8 @@ __global__ __launch_bounds__(1024, 1) void bb_k1t(bsls_bb_problem P, int64_t ite
         __syncthreads();
     }
     if (G == 1) {
-        k1_finish<ADD, REDUCE, FX>(P, iter, ITER, rb, (unsigned)T.nrb, r0, r1, 1, lds, part,
-                                   ticket, red, rmax);
+        k1_finish<ADD, REDUCE, FX, RW>(P, iter, ITER, rb, (unsigned)T.nrb, r0, r1, 1, lds, part,
+                                       ticket, red, rmax);
         PH(6);
         PH_FLUSH(PH_K1);
         return;
@@ -1389,6 +1441,16 @@ static int64_t k1_row_blocks(const bsls_bb_problem &P) {
 template <int MODE, bool ADD, bool REDUCE, bool ITER>
 static void launch_k1_mode(const bsls_bb_problem &P, int64_t iter, const BBWork &w,
                            hipStream_t st, int64_t rb0, int64_t rb1) {
+    if constexpr (ADD && (REDUCE || !ITER)) {
+        // roww: the weighted finish (the same launches as fx_sums covers on the tiles)
+        if (P.roww) {
+            allow_lds(bb_k1<MODE, ITER, true, REDUCE, true>);
+            bb_k1<MODE, ITER, true, REDUCE, true><<<(int)(P.A.ngroups * (rb1 - rb0)), 1024,
+                                                    panel_lds_bytes(P.A), st>>>(P, iter, w.tkrb,
+                                                                                w.p1, w.tk1, rb0);
+            return;
+        }
+    }
     allow_lds(bb_k1<MODE, ITER, ADD, REDUCE>);
     bb_k1<MODE, ITER, ADD, REDUCE><<<(int)(P.A.ngroups * (rb1 - rb0)), 1024, panel_lds_bytes(P.A),
                                      st>>>(P, iter, w.tkrb, w.p1, w.tk1, rb0);
@@ -1417,23 +1479,25 @@ static bool k1_init_folded(const bsls_bb_problem &P) {
 }
 
 // bb_k1_sum behind a several-group bb_k1t over row blocks [rb0, rb1): rows in
-// 16-B pairs (W = 2) where every pair is aligned in rpart, target and r
-template <bool ITER, bool ADD, bool REDUCE, bool FX>
+// 16-B pairs (W = 2) where every pair is aligned in rpart, target, r and (RW)
+// roww
+template <bool ITER, bool ADD, bool REDUCE, bool FX, bool RW = false>
 static void launch_k1_sum(const bsls_bb_problem &P, int64_t iter, const BBWork &w, hipStream_t st,
                           int64_t rb0, int64_t rb1) {
     const int64_t r0 = rb0 * P.At.H, r1 = (rb1 * P.At.H < P.m) ? rb1 * P.At.H : P.m;
     constexpr int K1_SUM_GRID = 1024;
     const bool pairs = !(P.m & 1) && !(r0 & 1) && r1 - r0 >= 2 &&
-                       !(((uintptr_t)P.rpart | (uintptr_t)P.target | (uintptr_t)P.r) & 15);
+                       !(((uintptr_t)P.rpart | (uintptr_t)P.target | (uintptr_t)P.r |
+                          (RW ? (uintptr_t)P.roww : (uintptr_t)0)) & 15);
     const int gk = grid_for(pairs ? (r1 - r0) / 2 : r1 - r0, 256);
     const int grid = (REDUCE && gk > K1_SUM_GRID) ? K1_SUM_GRID : gk;
     unsigned long long *rmax = FX ? w.rmax : nullptr;
     if (pairs)
-        bb_k1_sum<ITER, ADD, REDUCE, 2, FX><<<grid, 256, 0, st>>>(P, iter, P.At.ngroups, r0, r1,
-                                                                  w.pf, w.tkf, rmax);
+        bb_k1_sum<ITER, ADD, REDUCE, 2, FX, RW><<<grid, 256, 0, st>>>(P, iter, P.At.ngroups, r0,
+                                                                      r1, w.pf, w.tkf, rmax);
     else
-        bb_k1_sum<ITER, ADD, REDUCE, 1, FX><<<grid, 256, 0, st>>>(P, iter, P.At.ngroups, r0, r1,
-                                                                  w.pf, w.tkf, rmax);
+        bb_k1_sum<ITER, ADD, REDUCE, 1, FX, RW><<<grid, 256, 0, st>>>(P, iter, P.At.ngroups, r0,
+                                                                      r1, w.pf, w.tkf, rmax);
 }
 
 // K1 with fixed-point row sums (bsls_bb_problem.fx_sums): bb_k1t's FX form and,
@@ -1476,6 +1540,24 @@ static void launch_k1t_mode(const bsls_bb_problem &P, int64_t iter, const BBWork
         // walk, and the finish that keeps max|r|
         if (P.fx_sums) {
             launch_k1t_fx<MODE, REDUCE, ITER>(P, iter, w, st, rb0, rb1);
+            return;
+        }
+        // roww (check_problem: never with fx_sums or the atomic K1): one group
+        // finishes weighted in the walk's kernel; several leave the float
+        // form's partials, and bb_k1_sum weighs
+        if (P.roww) {
+            const int grid = (int)((rb1 - rb0) * P.At.ngroups);
+            const size_t lds = tile_lds_doubles(P.At, false) * 8;
+            if (P.At.ngroups > 1) {
+                allow_lds(bb_k1t<MODE, ITER, true, REDUCE>);
+                bb_k1t<MODE, ITER, true, REDUCE><<<grid, BSLS_TILE_THREADS, lds, st>>>(
+                    P, iter, w.p1, w.tk1, rb0);
+                launch_k1_sum<ITER, true, REDUCE, false, true>(P, iter, w, st, rb0, rb1);
+            } else {
+                allow_lds(bb_k1t<MODE, ITER, true, REDUCE, false, false, true>);
+                bb_k1t<MODE, ITER, true, REDUCE, false, false, true>
+                    <<<grid, BSLS_TILE_THREADS, lds, st>>>(P, iter, w.p1, w.tk1, rb0);
+            }
             return;
         }
     }
@@ -1657,6 +1739,9 @@ static int check_problem(const bsls_bb_problem *p) {
             return BSLS_E_ARG;
         if (!bound(p->fx_a1) || !bound(p->fx_a2) || !bound(p->x_bound)) return BSLS_E_ARG;
     }
+    // row weights: the whole problem on this GCD, float row sums, ordered group sums
+    if (p->roww && (p->shard_role != 0 || p->r_fx != 0.0 || p->fx_sums != 0 || p->k1_atomic == 2))
+        return BSLS_E_ARG;
     if (p->At.ent) {
         if (!tiles_valid(p->At, p->m, p->n, 0, general, false, PANEL_LDS_MAX)) return BSLS_E_ARG;
         if (p->At.ngroups > 1 && !p->rpart) return BSLS_E_ARG;
@@ -1681,11 +1766,11 @@ static int check_problem(const bsls_bb_problem *p) {
     return BSLS_OK;
 }
 
-// the entry points that fx_sums does not cover (include/bsls_hip.h)
+// the entry points that fx_sums and roww do not cover (include/bsls_hip.h)
 static int check_problem_float(const bsls_bb_problem *p) {
     const int rc = check_problem(p);
     if (rc != BSLS_OK) return rc;
-    return p->fx_sums ? BSLS_E_ARG : BSLS_OK;
+    return (p->fx_sums || p->roww) ? BSLS_E_ARG : BSLS_OK;
 }
 
 }  // namespace bsls
@@ -1742,6 +1827,8 @@ extern "C" int bsls_bb_stage(const bsls_bb_problem *p, int stage, int64_t iter, 
     // fx_sums: the single-GCD stages only (0, 3-7, 9)
     if (P.fx_sums && (stage == 1 || stage == 2 || stage == 8 || (stage >= 10 && stage <= 15)))
         return BSLS_E_ARG;
+    // roww: 0, 1 and 3-7 (stage 1, without target, stays the unweighted A x)
+    if (P.roww && (stage == 2 || (stage >= 8 && stage <= 15))) return BSLS_E_ARG;
     switch (stage) {
         case 0:  // reset scalars and tickets
             BSLS_CHECK(hipMemsetAsync(P.scal, 0, BSLS_S_COUNT * sizeof(double), st));

@@ -921,6 +921,25 @@ def fixed_sums_check(deterministic, tile_layouts, fmt, link_parts):
         raise ValueError('fixed_sums does not cover link parts')
 
 
+def row_weights_check(w, m):
+    """Per-link weights as m finite, non-negative float64 values on the host
+    (None stays None); anything else is a ValueError.  Pure host: runs before
+    anything touches the device."""
+    if w is None:
+        return None
+    if hasattr(w, 'detach'):              # a tensor, host or device
+        w = w.detach().cpu().numpy()
+    w = np.ascontiguousarray(np.asarray(w, dtype=np.float64).reshape(-1))
+    if w.size != int(m):
+        raise ValueError('row_weights has %d entries, expected one per row of A (%d)'
+                         % (w.size, int(m)))
+    if not np.all(np.isfinite(w)):
+        raise ValueError('row_weights must be finite (no NaN or inf)')
+    if np.any(w < 0):
+        raise ValueError('row_weights must be non-negative')
+    return w
+
+
 def fixed_plan_fits(plan, halo):
     """Whether a tile plan (H, groups, order) leaves the LDS room for the two
     words per row of the fixed-point sums."""
@@ -939,7 +958,7 @@ class BBEngine:
     def __init__(self, A, b, block_sizes, options=None, early_exit=True, A_dev=None,
                  AT_dev=None, AT=None, target=None, x0=None, general=False, fmt=None,
                  tile_plans=(None, None), colv=None, deterministic=False, tile_layouts=None,
-                 link_parts=None, fixed_sums=None):
+                 link_parts=None, fixed_sums=None, row_weights=None):
         # fixed_sums: order-free fixed-point row sums on the dealt tiles
         # (bsls_bb_problem.fx_sums) -- bit-reproducible iterates and exit
         # iterations from the default engine's walks.  None reads
@@ -954,6 +973,14 @@ class BBEngine:
         self.fixed_sums = bool(fixed_sums)
         if self.fixed_sums:
             fixed_sums_check(deterministic, tile_layouts, fmt, link_parts)
+        # row_weights: per-link weights w (bsls_bb_problem.roww; f = 0.5 sum w r^2),
+        # a 0/1 mask for a held-out fold -- set_row_weights swaps them between
+        # solves on the same images.  Checked here, installed once target is formed.
+        self.row_weights = None
+        row_weights = row_weights_check(row_weights, sps.csr_matrix(A).shape[0])
+        if row_weights is not None and self.fixed_sums:
+            raise ValueError('row_weights are not covered by fixed_sums: build the engine '
+                             'without one of them')
         torch = _torch()
         L = _native.lib()
         self.layout = lay = BlockLayout(block_sizes)
@@ -1161,8 +1188,10 @@ class BBEngine:
             self.x.copy_(self.colv * xin if self.scaled else xin)
             if self.fixed_sums:
                 self.set_x_bound(float(self.x.abs().max().item()))
-            self.stage(7, 0)                       # r = A x0 + (-b)
+            self.stage(7, 0)                       # r = A x0 + (-b), unweighted
             self.target.copy_(self.r)
+        if row_weights is not None:
+            self.set_row_weights(row_weights)
 
     @property
     def A(self):
@@ -1200,6 +1229,43 @@ class BBEngine:
             slots = self.work[self._rmax_off:self._rmax_off + 8 * n].view(torch.float64)
             slots.zero_()
             slots[0] = self.r.abs().max()      # (the bit pattern the kernels' atomic max keeps)
+
+    def set_row_weights(self, w):
+        """Per-link weights for what runs next: m finite values >= 0 (host or
+        device memory, copied to a device tensor the engine keeps), or None
+        for the unweighted problem.  A pointer swap: the images, the workspace
+        and target stay, and solve()'s prologue resets the scalars, so one
+        engine serves every fold of a cross-validation.  The objective becomes
+        f = 0.5 sum_i w_i r_i^2; rows with w_i == 0 are held out and their
+        0.5 sum r_i^2 is held_out()."""
+        w = row_weights_check(w, self.m)
+        if w is None:
+            self.row_weights = None
+            self.P.roww = None
+            return
+        if self.fixed_sums:
+            raise ValueError('row_weights are not covered by fixed_sums: build the engine '
+                             'without one of them')
+        if self.P.shard_role != 0 or self.P.r_fx > 0:
+            raise ValueError('row_weights are not covered on a column shard')
+        if self.P.k1_atomic == 2:
+            raise ValueError('row_weights keep the ordered group sums: BSLS_K1_ATOMIC=1 '
+                             'does not go with them')
+        torch = _torch()
+        self.row_weights = torch.from_numpy(w).cuda()
+        self.P.roww = self.row_weights.data_ptr()
+
+    def held_out(self):
+        """0.5 sum of r_i^2 over the rows with weight 0 (r the plain residual)
+        at the last solve() / f(z); 0.0 on an unweighted engine."""
+        if self.row_weights is None:
+            return 0.0
+        return 0.5 * float(self.scal[_native.S_HELD].item())
+
+    def _unweighted_only(self, what):
+        if self.row_weights is not None:
+            raise ValueError('%s is not covered by row_weights (BB only): '
+                             'set_row_weights(None) first' % what)
 
     def _fixed_only_bb(self, what):
         if self.fixed_sums:
@@ -1251,6 +1317,7 @@ class BBEngine:
         scale = float(scale)
         if scale > 0:
             self._fixed_only_bb('a fixed-point r')
+        self._unweighted_only('a fixed-point r')
         if scale < 0 or (scale > 0 and not self.fixed_r_ok()):
             raise ValueError('fixed-point r needs an atomic sharded K1 (fixed_r_ok)')
         self.P.r_fx = scale
@@ -1276,6 +1343,7 @@ class BBEngine:
             raise ValueError('shard role must be 0, 1 or 2')
         if role != 0:
             self._fixed_only_bb('a column shard')
+            self._unweighted_only('a column shard')
         self.P.shard_role = int(role)
 
     def row_blocks(self):
@@ -1339,7 +1407,9 @@ class BBEngine:
         self.stage(6, 0)
 
     def apply_A(self, z, alpha=1.0):
-        """alpha A N z (DORE's linop with A scaled by alpha, gradient_descent.py:57-63)."""
+        """alpha A N z (DORE's linop with A scaled by alpha, gradient_descent.py:57-63).
+        Unweighted, as apply_A_x and apply_AT: row_weights act on residual, f
+        and nabla_f only."""
         self._fixed_only_bb('apply_A (DORE)')
         self._x_of(z)
         self.stage(1, 0)
@@ -1353,19 +1423,22 @@ class BBEngine:
         return g * alpha if alpha != 1.0 else g.clone()
 
     def residual(self, z, alpha=1.0):
-        """alpha (A N z + target) (DORE scales A and target by alpha)."""
+        """alpha (A N z + target) (DORE scales A and target by alpha); with
+        row_weights w the weighted residual, alpha w * (A N z + target)."""
         self._x_of(z)
         self.stage(7, 0)
         return self.r * alpha if alpha != 1.0 else self.r.clone()
 
     def f(self, z):
-        """0.5 ||A N z + target||^2 (main.py:53), f as K1's finish forms it."""
+        """0.5 ||A N z + target||^2 (main.py:53), f as K1's finish forms it; with
+        row_weights w, 0.5 sum w_i r_i^2 (and held_out() the zero-weight rows')."""
         self._x_of(z)
         self.stage(7, 0)
         return float(self.scal[_native.S_FX].item())
 
     def nabla_f(self, z):
-        """N' A' (A N z + target) (main.py:54)."""
+        """N' A' (A N z + target) (main.py:54); with row_weights w,
+        N' A' (w * (A N z + target))."""
         self._x_of(z)
         self.stage(7, 0)
         self.stage(3, 0)
@@ -1374,6 +1447,7 @@ class BBEngine:
     def line_search(self):
         """This engine's device weak Wolfe line search (LBFGS.solve)."""
         self._fixed_only_bb('the line search')
+        self._unweighted_only('the line search')
         ls = getattr(self, '_ls', None)
         if ls is None:
             ls = self._ls = LineSearch(self)

@@ -112,6 +112,9 @@ class ShardedBB:
 
     def __init__(self, engine, all_reduce, parts=1, all_reduce_async=None, rank=None,
                  fuse=None, native=None, slices=None):
+        if getattr(engine, 'row_weights', None) is not None:
+            raise ValueError('a column shard is not covered by row_weights: '
+                             'set_row_weights(None) first')
         self.e = engine
         rank = _shard_rank(rank)
         # link parts: an engine built with link_parts = parts (K2's image in

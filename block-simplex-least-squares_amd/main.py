@@ -44,6 +44,9 @@ def parser():
                      help='the default engine\'s dealt tiles with order-free fixed-point row '
                           'sums (bit-reproducible runs and exit iterations, method BB only); '
                           'also BSLS_FIXED_SUMS=1')
+    p.add_argument('--cv', dest='cv', type=int, default=None, metavar='K',
+                   help='after the run, K-fold cross-validation over the links on the same '
+                        'engine (cross_validation.kfold; method BB only): output[\'cv\']')
     return p
 
 
@@ -54,25 +57,32 @@ def deterministic_default():
     return os.environ.get('BSLS_DETERMINISTIC', '0') not in ('', '0')
 
 
-def build_engine(A, b, x0, block_sizes, options=None, deterministic=None, reproducible=None):
+def build_engine(A, b, x0, block_sizes, options=None, deterministic=None, reproducible=None,
+                 row_weights=None):
     """The device engine of solve_in_z's closures.  deterministic=True keeps
     every SpMV row sum in a fixed order (panels / thread-stream tiles): runs are
     bit-reproducible, so the exact-zero exit of BB.py:22 and the exit iteration
     repeat run to run; the default (dealt tiles, LDS atomic row sums) is faster
     and reproducible to ~1e-16.  reproducible=True keeps the dealt tiles and
     sums their rows in fixed point instead (order-free: bit-reproducible too;
-    BB only); None leaves it to BSLS_FIXED_SUMS (BBEngine(fixed_sums=None))."""
+    BB only); None leaves it to BSLS_FIXED_SUMS (BBEngine(fixed_sums=None)).
+    row_weights: per-link weights w, f = 0.5 sum w_i r_i^2 (BB only; not with
+    reproducible)."""
     from device import BBEngine
     if deterministic is None:
         deterministic = deterministic_default() and not reproducible
     return BBEngine(A, b, block_sizes, options=options, x0=x0, deterministic=bool(deterministic),
-                    fixed_sums=(True if reproducible else None))
+                    fixed_sums=(True if reproducible else
+                                (False if row_weights is not None else None)),
+                    row_weights=row_weights)
 
 
-def solve_in_z(A, b, x0, N, block_sizes, method, options=None, engine=None, deterministic=None):
+def solve_in_z(A, b, x0, N, block_sizes, method, options=None, engine=None, deterministic=None,
+               row_weights=None):
     """python/main.py:41-79 on the device.  N is accepted for signature
     compatibility and never used: the engine applies N / N' as per-block
-    differences without materialising it."""
+    differences without materialising it.  row_weights (BB only) go to the
+    engine built here; an engine passed in keeps its own."""
     if block_sizes is not None and len(block_sizes) == A.shape[1]:
         logging.error('Trivial example: nblocks == nroutes, exiting solver')
         sys.exit()
@@ -81,7 +91,8 @@ def solve_in_z(A, b, x0, N, block_sizes, method, options=None, engine=None, dete
     # (c_extensions.pyx:78 through main.py:64): every block needs >= 2 routes
     assert np.all(block_sizes >= 2)
     z0 = x2z(x0, block_sizes)
-    eng = engine or build_engine(A, b, x0, block_sizes, deterministic=deterministic)
+    eng = engine or build_engine(A, b, x0, block_sizes, deterministic=deterministic,
+                                 row_weights=row_weights)
     gd = GradientDescent(z0=z0, method=method, options=options, engine=eng)
     iters, times, states = gd.run()
     import torch
@@ -91,11 +102,12 @@ def solve_in_z(A, b, x0, N, block_sizes, method, options=None, engine=None, dete
     return iters, times, states
 
 
-def solve_in_z_cpu(A, b, x0, N, block_sizes, method, options=None):
+def solve_in_z_cpu(A, b, x0, N, block_sizes, method, options=None, row_weights=None):
     """python/main.py:41-79 on the host (BASELINE configs[0]): the reference's
     closures over SciPy csr_matvec, proj = the host c_extensions library's
     isotonic_regression_multi (include/bsls_cpu.h) + clip, the solver loops of
-    BB.py / LBFGS.py / DORE.py over them."""
+    BB.py / LBFGS.py / DORE.py over them.  row_weights w (BB only): the
+    engine's weighted objective, f = 0.5 sum w r^2, nabla_f = N'A'(w r)."""
     import numpy.linalg as la
     from bsls_utils import particular_x0
     from c_extensions import _cpu
@@ -108,8 +120,22 @@ def solve_in_z_cpu(A, b, x0, N, block_sizes, method, options=None):
     target = A.dot(x0) - b
     AT = A.T.tocsr()
     NT = N.T.tocsr()
-    f = lambda z: 0.5 * la.norm(A.dot(N.dot(z)) + target) ** 2
-    nabla_f = lambda z: NT.dot(AT.dot(A.dot(N.dot(z)) + target))
+    if row_weights is not None:
+        from device import row_weights_check
+        if method != 'BB':
+            raise ValueError('row_weights cover method BB only (got %r)' % method)
+        w = row_weights_check(row_weights, A.shape[0])
+
+        def f(z):
+            r = A.dot(N.dot(z)) + target
+            return 0.5 * np.sum(w * r * r)
+
+        def nabla_f(z):
+            r = A.dot(N.dot(z)) + target
+            return NT.dot(AT.dot(w * r))
+    else:
+        f = lambda z: 0.5 * la.norm(A.dot(N.dot(z)) + target) ** 2
+        nabla_f = lambda z: NT.dot(AT.dot(A.dot(N.dot(z)) + target))
     cum_blocks = np.concatenate(([0], np.cumsum(block_sizes - 1)))
 
     def proj(x):
@@ -237,6 +263,11 @@ def main(args=None, plot=False):
         raise ValueError('--reproducible covers --method BB only (got %r)' % args.method)
     if reproducible and getattr(args, 'deterministic', None):
         raise ValueError('--reproducible and --deterministic exclude each other')
+    cv = getattr(args, 'cv', None)
+    if cv is not None and args.method != 'BB':
+        raise ValueError('--cv covers --method BB only (got %r)' % args.method)
+    if cv is not None and reproducible:
+        raise ValueError('--cv and --reproducible exclude each other')
     if args.log in ACCEPTED_LOG_LEVELS:
         logging.basicConfig(level=getattr(logging, args.log))
     config = {'full': True, 'L': True, 'OD': True, 'CP': True, 'LP': True,
@@ -257,6 +288,9 @@ def main(args=None, plot=False):
         iters, times, states = solve_in_z_cpu(AA, bb, x0, N, block_sizes, args.method)
         x_last, error, output = LS_postprocess_cpu(states, x0, AA, bb, x_split, scaling=scaling,
                                                    block_sizes=block_sizes, N=N, output=output)
+        if cv is not None:
+            from cross_validation import kfold
+            output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, device='cpu')
         return iters, times, states, output
     eng = build_engine(AA, bb, x0, block_sizes,
                        deterministic=getattr(args, 'deterministic', None),
@@ -265,6 +299,9 @@ def main(args=None, plot=False):
     x_last, error, output = LS_postprocess(states, x0, AA, bb, x_split, scaling=scaling,
                                            block_sizes=block_sizes, N=N, output=output,
                                            engine=eng)
+    if cv is not None:
+        from cross_validation import kfold
+        output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, engine=eng)
     if plot:
         import matplotlib.pyplot as plt
         plt.figure(); plt.hist(x_last)

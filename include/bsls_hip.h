@@ -190,7 +190,9 @@ enum {
     BSLS_S_WARN = 10,      /* count of |t| outside [1e-10, 1e10] (BB.py:27-28) */
     BSLS_S_PSUMDG = 11,    /* stage 10: iteration i - 1's SUMDG, DZDG, DGDG, GG (11..14) */
     BSLS_S_PDZDG = 12, BSLS_S_PDGDG = 13, BSLS_S_PGG = 14,
-    BSLS_S_DD = 15,        /* unused (was sy_dr's ||r - r_prev||^2, retired in round 6) */
+    BSLS_S_HELD = 15,      /* bsls_bb_problem.roww: sum of o_i^2 over the rows with w_i == 0
+                              at the last K1 finish that reduced; never written without roww */
+    BSLS_S_DD = 15,        /* the slot's earlier name (sy_dr's ||r - r_prev||^2, retired) */
     BSLS_S_COUNT = 16
 };
 enum {
@@ -451,6 +453,24 @@ typedef struct bsls_bb_problem {
      * bsls_lsq_op.x_bound: max|colv| in iterations (|N z| <= 1 after K3's
      * clip), 2 (max|z0| + 1) max|colv| for the prologue. */
     double x_bound;
+    /* m per-link weights w_i >= 0 (finite), or NULL: everything as without
+     * them.  Set, the objective is f = 0.5 sum_i w_i o_i^2 with o = A N z +
+     * target the plain residual: every K1 finish that adds target and either
+     * reduces or runs outside an iteration (the iteration's K1, stage 7, the
+     * prologue's two) stores r_i = w_i o_i -- an exact +0.0 where w_i == 0,
+     * whatever o_i is -- so K2 gathers the weighted residual, scal[RR] =
+     * sum_{w_i != 0} o_i (w_i o_i), and scal[BSLS_S_HELD] = sum_{w_i == 0}
+     * o_i^2, the hold-out error of a 0/1 mask, written beside RR.  The matrix
+     * images, K2, K3 and the workspace are the unweighted problem's, so
+     * swapping the pointer between solves rebuilds nothing.  Stage 1 (no
+     * target) stays unweighted.  Needs shard_role 0, r_fx 0, fx_sums 0 and
+     * k1_atomic != 2; anything else is BSLS_E_ARG.
+     * Entry points that reject a weighted problem (BSLS_E_ARG):
+     * bsls_dore_iterate, bsls_lbfgs_ls_begin / _trials / _finish,
+     * bsls_bb_k2_part, bsls_bb_k1_rows, bsls_bb_residual_rows,
+     * bsls_bb_shard_iterate, bsls_bb_shard_iterate_parts, and bsls_bb_stage 2,
+     * 8, 9 and 10-15. */
+    const double *roww;
 } bsls_bb_problem;
 
 size_t bsls_bb_workspace_size(int64_t m, int64_t n, int64_t nz);
