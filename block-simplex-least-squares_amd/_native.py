@@ -90,6 +90,20 @@ class BBProblem(ctypes.Structure):
                 ('x_bound', _dbl), ('roww', _vp)]
 
 
+class BBMProblem(ctypes.Structure):
+    """Mirror of struct bsls_bbm_problem (include/bsls_hip.h)."""
+    _fields_ = [('m', _i64), ('n', _i64), ('nz', _i64), ('nblocks', _i64),
+                ('R', _i64), ('RP', _i64),
+                ('a_indptr', _vp), ('a_indices', _vp), ('a_val', _vp), ('a_nnz', _i64),
+                ('at_indptr', _vp), ('at_indices', _vp), ('at_val', _vp), ('at_nnz', _i64),
+                ('target', _vp), ('roww', _vp), ('xz', _vp), ('zx', _vp),
+                ('pk_start', _vp), ('pk_mask', _vp), ('pk_len', _vp), ('npacks', _i64),
+                ('long_packs', _vp), ('nlong', _i64), ('iso_work', _vp), ('iso_work_bytes', _sz),
+                ('z', _vp * 2), ('g', _vp * 2), ('dz', _vp), ('y', _vp), ('x', _vp), ('w', _vp),
+                ('r', _vp), ('scal', _vp), ('work', _vp), ('work_bytes', _sz),
+                ('max_iter', _i64), ('opt_tol', _dbl), ('early_exit', _i32), ('reserved', _i32)]
+
+
 class DoreState(ctypes.Structure):
     """Mirror of struct bsls_dore_state (include/bsls_hip.h)."""
     _fields_ = [('X', _vp * 3), ('X1', _vp), ('D', _vp), ('X2', _vp), ('AX', _vp * 3),
@@ -197,6 +211,10 @@ _SIGS = {
     'bsls_dore_iterate': (_int, [ctypes.POINTER(BBProblem), ctypes.POINTER(DoreState), _i64,
                                  _i64, _vp]),
     'bsls_bb_stage': (_int, [ctypes.POINTER(BBProblem), _int, _i64, _vp]),
+    'bsls_bbm_workspace_size': (_sz, [_i64, _i64, _i64, _i64]),
+    'bsls_bbm_prologue': (_int, [ctypes.POINTER(BBMProblem), _vp]),
+    'bsls_bbm_iterate': (_int, [ctypes.POINTER(BBMProblem), _i64, _i64, _vp]),
+    'bsls_bbm_stage': (_int, [ctypes.POINTER(BBMProblem), _int, _i64, _vp]),
     'bsls_lbfgs_ls_work_size': (_sz, [_i64]),
     'bsls_lbfgs_ls_begin': (_int, [ctypes.POINTER(BBProblem), ctypes.POINTER(LsState), _vp]),
     'bsls_lbfgs_ls_trials': (_int, [ctypes.POINTER(BBProblem), ctypes.POINTER(LsState), _i64,

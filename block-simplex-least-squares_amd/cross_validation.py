@@ -83,8 +83,38 @@ def _kfold_cpu(A, b, x0, N, block_sizes, masks, options):
     return out
 
 
+def _kfold_batch(A, b, x0, block_sizes, masks, options, batch):
+    """The folds `batch` at a time on one device.BatchBB (balanced chunks,
+    device.batch_groups); a fold's seconds is its chunk's time divided by the
+    chunk's size."""
+    import _native
+    from bsls_utils import x2z
+    from device import BatchBB, batch_groups
+    z0 = x2z(x0, block_sizes)
+    out = []
+    eng, lo = None, 0
+    for size in batch_groups(len(masks), batch):
+        chunk = masks[lo:lo + size]
+        lo += size
+        t0 = time.time()
+        if eng is None or eng.R != size:
+            eng = BatchBB(A, [b] * size, block_sizes, row_weights=chunk, options=options, x0=x0)
+        else:
+            for j, w in enumerate(chunk):
+                eng.set_row_weights(j, w)
+        zs = eng.solve(z0=[z0] * size)
+        S, held = eng.scalars(), eng.held_out()
+        dt = (time.time() - t0) / size
+        for j in range(size):
+            out.append({'iters': int(eng.iterations[j]),
+                        'stop': _native.STOP_TEXT[int(eng.stop_reasons[j])],
+                        'f_train': float(S[j, _native.S_FX]), 'held_out': held[j],
+                        'z': zs[j], 'seconds': dt})
+    return out
+
+
 def kfold(A, b, x0, N, block_sizes, k, options=None, device='gpu', engine=None, shuffle=False,
-          seed=0, deterministic=None):
+          seed=0, deterministic=None, batch=None):
     """K-fold cross-validation of the z-space BB fit: fold i holds out the rows
     where kfold_masks(m, k)[i] is 0, fits the rest from z0 = x2z(x0) and scores
     0.5 ||A_test x - b_test||^2 on the held-out rows.  Returns one dict per
@@ -94,7 +124,20 @@ def kfold(A, b, x0, N, block_sizes, k, options=None, device='gpu', engine=None, 
     put back afterwards) or one built here -- and held_out is the engine's own
     (BBEngine.held_out), not recomputed.  device='cpu': main.solve_in_z_cpu
     per fold over SciPy.  options: the solver's (max_iter, opt_tol); None keeps
-    the engine's on 'gpu' and GradientDescent's defaults on 'cpu'."""
+    the engine's on 'gpu' and GradientDescent's defaults on 'cpu'.
+
+    batch: None (the sequential path above), or an int in 1..8: the folds run
+    `batch` at a time in lockstep on one device.BatchBB (plain CSR images of A
+    and A', every sum in a fixed order; `engine` and `deterministic` are not
+    used).  Same keys; seconds is the chunk's time divided by its size.
+    device='cpu' accepts and ignores it.  Measured on C3 (profiles/batch_bb_C3.txt): the batch costs
+    147.9 us per iteration and problem at batch = 8 (342.6 at 1) against the
+    fused engine's 73.5 us, so the sequential path is the faster one and stays
+    the default; batch buys lockstep fits that repeat bit for bit."""
+    if batch is not None:
+        if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) \
+                or not 1 <= batch <= 8:
+            raise ValueError('batch must be None or an int in 1..8 (got %r)' % (batch,))
     from bsls_utils import x2z
     block_sizes = np.asarray(block_sizes)
     masks = kfold_masks(A.shape[0], k, shuffle=shuffle, seed=seed)
@@ -102,6 +145,8 @@ def kfold(A, b, x0, N, block_sizes, k, options=None, device='gpu', engine=None, 
         return _kfold_cpu(A, b, x0, N, block_sizes, masks, options)
     if device != 'gpu':
         raise ValueError("device must be 'gpu' or 'cpu' (got %r)" % (device,))
+    if batch is not None:
+        return _kfold_batch(A, b, x0, block_sizes, masks, options, int(batch))
     import torch
     import _native
     from main import build_engine

@@ -47,6 +47,9 @@ def parser():
     p.add_argument('--cv', dest='cv', type=int, default=None, metavar='K',
                    help='after the run, K-fold cross-validation over the links on the same '
                         'engine (cross_validation.kfold; method BB only): output[\'cv\']')
+    p.add_argument('--cv-batch', dest='cv_batch', type=int, default=None, metavar='R',
+                   help='with --cv: run the folds R (1..8) at a time in lockstep on one batched '
+                        'engine (device.BatchBB) instead of one after another')
     return p
 
 
@@ -100,6 +103,42 @@ def solve_in_z(A, b, x0, N, block_sizes, method, options=None, engine=None, dete
     x = eng.n_apply(zl, with_x0=True).cpu().numpy()   # particular_x0 + N z
     assert np.all(x >= 0), "x shouldn't have negative entries after projection"
     return iters, times, states
+
+
+def solve_many(A, bs, x0, N, block_sizes, options=None, row_weights=None, batch=8):
+    """solve_in_z's BB fit for many right-hand sides over one network (the
+    --noise draws of python/main.py:164-166, the same links at several times
+    of day): the problems run `batch` (1..8) at a time in lockstep on
+    device.BatchBB, in balanced groups.  bs: a sequence of vectors or an m x K
+    array; row_weights: None or one entry (None or a weight vector) per b.
+    Returns [(iters, stop, z)] in the order of bs, stop the message of
+    _native.STOP_TEXT.  N is accepted for the signature and never used."""
+    import _native
+    from device import BatchBB, batch_groups, batch_width
+    batch_width(batch)
+    block_sizes = np.asarray(block_sizes)
+    if hasattr(bs, 'ndim') and bs.ndim == 2:
+        bs = [np.asarray(bs)[:, j] for j in range(bs.shape[1])]
+    bs = list(bs)
+    if row_weights is None:
+        row_weights = [None] * len(bs)
+    if len(row_weights) != len(bs):
+        raise ValueError('row_weights has %d entries for %d problems' % (len(row_weights), len(bs)))
+    z0 = x2z(x0, block_sizes)
+    out, eng, lo = [], None, 0
+    for size in batch_groups(len(bs), batch):
+        chunk, wts = bs[lo:lo + size], list(row_weights[lo:lo + size])
+        lo += size
+        if eng is None or eng.R != size:
+            eng = BatchBB(A, chunk, block_sizes, row_weights=wts, options=options, x0=x0)
+        else:
+            for j in range(size):
+                eng.set_b(j, chunk[j])
+                eng.set_row_weights(j, wts[j])
+        zs = eng.solve(z0=[z0] * size)
+        out += [(int(eng.iterations[j]), _native.STOP_TEXT[int(eng.stop_reasons[j])], zs[j])
+                for j in range(size)]
+    return out
 
 
 def solve_in_z_cpu(A, b, x0, N, block_sizes, method, options=None, row_weights=None):
@@ -268,6 +307,11 @@ def main(args=None, plot=False):
         raise ValueError('--cv covers --method BB only (got %r)' % args.method)
     if cv is not None and reproducible:
         raise ValueError('--cv and --reproducible exclude each other')
+    cv_batch = getattr(args, 'cv_batch', None)
+    if cv_batch is not None and cv is None:
+        raise ValueError('--cv-batch needs --cv')
+    if cv_batch is not None and not 1 <= cv_batch <= 8:
+        raise ValueError('--cv-batch takes 1..8 (got %r)' % (cv_batch,))
     if args.log in ACCEPTED_LOG_LEVELS:
         logging.basicConfig(level=getattr(logging, args.log))
     config = {'full': True, 'L': True, 'OD': True, 'CP': True, 'LP': True,
@@ -290,7 +334,7 @@ def main(args=None, plot=False):
                                                    block_sizes=block_sizes, N=N, output=output)
         if cv is not None:
             from cross_validation import kfold
-            output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, device='cpu')
+            output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, device='cpu', batch=cv_batch)
         return iters, times, states, output
     eng = build_engine(AA, bb, x0, block_sizes,
                        deterministic=getattr(args, 'deterministic', None),
@@ -301,7 +345,7 @@ def main(args=None, plot=False):
                                            engine=eng)
     if cv is not None:
         from cross_validation import kfold
-        output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, engine=eng)
+        output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, engine=eng, batch=cv_batch)
     if plot:
         import matplotlib.pyplot as plt
         plt.figure(); plt.hist(x_last)

@@ -914,6 +914,79 @@ int bsls_lbfgs_push(int64_t m, int64_t slot, double rho_new, double *d_state,
                     const double *d_dots, const double *d_y_new, const double *d_s_new,
                     double *d_y_slot, double *d_s_slot, int64_t n, void *stream);
 
+/* ---- batched z-space BB: R problems in lockstep over one image of A ----------
+ * R (1..8) problems that share A, the block layout and x0 and differ in b_j,
+ * in per-link weights w_j and in z0_j, each following BB.solve (python/BB.py:
+ * 14-42) under solvers.stopping (python/solvers.py:40-63) with its own step,
+ * objective, exit iteration and stop reason: the k folds of CrossValidation.py:
+ * 126-183, the --noise draws of main.py:164-166.  RP is R rounded up to 1, 2,
+ * 4 or 8.  x- and link-space vectors are interleaved (element i of problem j
+ * at [i * RP + j]: x, w, r, target, roww), so one column index of the matrix
+ * fetches RP contiguous doubles; z-space vectors are stacked (problem j at
+ * [j * nz, (j + 1) * nz): z, g, dz, y), so the planned PAVA
+ * (bsls_isotonic_packs over the z-block starts replicated RP times) serves the
+ * batch as it is.  A and A' are plain CSR with stored values.  scal is RP rows
+ * of BSLS_S_COUNT slots with the meanings of BSLS_S_*; the padding columns
+ * (j >= R) start stopped.  A stopped problem is frozen: none of its z, g, dz,
+ * x, r entries or scalars is written again (its z is z[scal[j][ZBUF]], its
+ * iteration scal[j][ITER]).  Every sum is reduced in a fixed order, without
+ * atomics on data: a run repeats bit for bit.  The caller owns every buffer. */
+typedef struct bsls_bbm_problem {
+    int64_t m, n, nz, nblocks;           /* A is m x n; nz = n - nblocks */
+    int64_t R, RP;                       /* problems; the interleave width */
+    const int64_t *a_indptr;             /* A: m + 1 */
+    const int32_t *a_indices;
+    const double *a_val;
+    int64_t a_nnz;
+    const int64_t *at_indptr;            /* A': n + 1 */
+    const int32_t *at_indices;
+    const double *at_val;
+    int64_t at_nnz;
+    const double *target;                /* m x RP: A x0 - b_j */
+    const double *roww;                  /* m x RP weights (ones where a problem has none), or
+                                            NULL: no problem is weighted, HELD is never written */
+    const int32_t *xz;                   /* n: x entry i's z index, -1 for a block's last entry */
+    const int32_t *zx;                   /* nz: z entry i's x index */
+    const int64_t *pk_start, *pk_mask;   /* the pack plan of the RP * nblocks stacked z-blocks */
+    const int32_t *pk_len;
+    int64_t npacks;
+    const int32_t *long_packs;
+    int64_t nlong;
+    void *iso_work;                      /* bsls_isotonic_workspace_size(RP * nz) when nlong > 0 */
+    size_t iso_work_bytes;
+    double *z[2], *g[2];                 /* RP * nz each, ping-pong by iteration parity */
+    double *dz, *y;                      /* RP * nz: z - z_prev; the step before projection */
+    double *x, *w;                       /* n x RP: N z; A' r */
+    double *r;                           /* m x RP: the weighted residual */
+    double *scal;                        /* RP x BSLS_S_COUNT */
+    void *work;                          /* bsls_bbm_workspace_size bytes */
+    size_t work_bytes;
+    int64_t max_iter;
+    double opt_tol;
+    int32_t early_exit, reserved;
+} bsls_bbm_problem;
+/* Bytes of `work` (partials of the two-stage sums and their tickets). */
+size_t bsls_bbm_workspace_size(int64_t m, int64_t n, int64_t nz, int64_t R);
+/* BB.py:16-20 for every problem: g_prev = nabla_f(z0 + 1) into g[0], then
+ * r(z0), ||r||^2 and f(z0); z[0] holds the z0_j on entry.  Resets scal. */
+int bsls_bbm_prologue(const bsls_bbm_problem *p, void *stream);
+/* Iterations first_iter .. first_iter + count - 1 of BB.py:21-40 for every
+ * running problem (A' r, the gradient and the BB sums, the step, PAVA, clip
+ * and x, then A x + target with f and solvers.stopping's test). */
+int bsls_bbm_iterate(const bsls_bbm_problem *p, int64_t first_iter, int64_t count,
+                     void *stream);
+/* One kernel of the step (main.py:53-65's closures, piece by piece), so each
+ * can be driven alone; iter <= 0 means outside an iteration (every column is
+ * written, no iteration is recorded and no stop test runs):
+ *   0 reset scal and the tickets           1 r = A x + target, finish (K1)
+ *   2 w = A' r                             3 g = N' w (+ dg, the sums, t)
+ *   4 y = z - t g                          5 PAVA of y
+ *   6 z = clip01(y), dz, x = N z           7 z[1] = z[0] + 1, dz, x = N z[1]
+ *   8 x = N z[0]
+ * Stages 3, 4, 6 at iter > 0 read z[(iter - 1) & 1] / g[(iter - 1) & 1] and
+ * write z[iter & 1] / g[iter & 1]; stage 3 at iter <= 0 writes g[0]. */
+int bsls_bbm_stage(const bsls_bbm_problem *p, int stage, int64_t iter, void *stream);
+
 /* Library / device info (for the loader's self-check). */
 const char *bsls_version(void);
 int bsls_device_arch(char *buf, int buflen);
