@@ -32,6 +32,23 @@ STOP_TEXT = {STOP_NOCHANGE: 'Exiting... no change in gradient',
              STOP_GRAD: 'Exiting... norm(grad) too small',
              STOP_DG: 'Exiting... no change in gradient'}
 
+# bsls_bb_stage's stage ids (enum bsls_stage, include/bsls_hip.h; 11 is unassigned)
+STAGE_RESET = 0
+STAGE_K1_PARTIAL = 1
+STAGE_R_FINISH_TARGET = 2
+STAGE_K2 = 3
+STAGE_K3 = 4
+STAGE_Z_PLUS_ONE = 5
+STAGE_Z2X = 6
+STAGE_K1 = 7
+STAGE_K2_R_FINISH = 8
+STAGE_R_FINISH = 9
+STAGE_K2_RR_SLICE = 10
+STAGE_RECORD = 12
+STAGE_K3_RECORD = 13
+STAGE_K1_PARTIAL_INITED = 14
+STAGE_K3_RECORD_INIT = 15
+
 _vp = ctypes.c_void_p
 # bsls_all_reduce_fn (include/bsls_hip.h): (d_buf, count, stream, user) -> 0 / error
 ALL_REDUCE_FN = ctypes.CFUNCTYPE(ctypes.c_int, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p,
@@ -58,7 +75,7 @@ class Panels(ctypes.Structure):
 
 TILE_THREADS = 1024       # BSLS_TILE_THREADS
 TILE_MAXSLOTS = 20        # BSLS_TILE_MAXSLOTS
-TILE_LDS_BYTES = 163840 - 512   # dynamic LDS a tile kernel may take (bb.hip PANEL_LDS_MAX)
+TILE_LDS_BYTES = 163840 - 512   # dynamic LDS a tile kernel may take (bb_launch.hpp PANEL_LDS_MAX)
 TILE_NT = 0x100                  # bsls_tiles.layout flag BSLS_TILE_NT
 TILE_VAL32, TILE_VAL16 = 0x200, 0x400   # BSLS_TILE_VAL32 / VAL16
 

@@ -198,7 +198,7 @@ extern "C" int bsls_dore_iterate(const bsls_bb_problem *p, const bsls_dore_state
         }();
         const bool top_k1 = i == 0 || recompute;
         if (top_k1) {
-            bb_z2x<<<grid_for(p->n, 256), 256, 0, st>>>(PS, x);
+            launch_bb_z2x(PS, x, st);
             launch_k1<false, false, true>(PS, i, w, st);
         }
         dore_top<<<gb, 256, 0, st>>>(PS, D, i, x, xp, top_k1 ? nullptr : axp);

@@ -238,26 +238,30 @@ extern "C" int bsls_bb_shard_iterate(const bsls_bb_problem *p, bsls_comm *c, int
         if (fuse == 2) {
             // K2 with this rank's slice of ||r||^2, the five sums over ranks,
             // then f and the stop test of i - 1
-            // (stage 13: K3 with stage 12 -- f and the stop test of i - 1 --
+            // (K3_RECORD: K3 with RECORD -- f and the stop test of i - 1 --
             // folded in)
-            // (stage 15: 13 with the next K1's r initialisation folded in when
-            // K1 adds its group sums by atomics; stage 14 is then stage 1 without it)
-            if ((rc = bsls_bb_stage(p, 10, i, stream)) != BSLS_OK) return rc;
+            // (K3_RECORD_INIT: that with the next K1's r initialisation folded
+            // in when K1 adds its group sums by atomics; K1_PARTIAL_INITED is
+            // then K1_PARTIAL without it)
+            if ((rc = bsls_bb_stage(p, BSLS_STAGE_K2_RR_SLICE, i, stream)) != BSLS_OK) return rc;
             if ((rc = all_reduce(p->scal + BSLS_S_SUMDG, 5)) != BSLS_OK) return rc;
-            if ((rc = bsls_bb_stage(p, 15, i, stream)) != BSLS_OK) return rc;
+            if ((rc = bsls_bb_stage(p, BSLS_STAGE_K3_RECORD_INIT, i, stream)) != BSLS_OK) return rc;
         } else {
             // K2 (+ the fused f / stop test of i - 1), then the BB sums over ranks
-            if ((rc = bsls_bb_stage(p, fuse ? 8 : 3, i, stream)) != BSLS_OK) return rc;
+            const int k2 = fuse ? BSLS_STAGE_K2_R_FINISH : BSLS_STAGE_K2;
+            if ((rc = bsls_bb_stage(p, k2, i, stream)) != BSLS_OK) return rc;
             if ((rc = all_reduce(p->scal + BSLS_S_SUMDG, 4)) != BSLS_OK) return rc;
-            if ((rc = bsls_bb_stage(p, 4, i, stream)) != BSLS_OK) return rc;
+            if ((rc = bsls_bb_stage(p, BSLS_STAGE_K3, i, stream)) != BSLS_OK) return rc;
         }
         // the partial residual, then r = the sum over ranks (the one real exchange)
-        if ((rc = bsls_bb_stage(p, fuse == 2 ? 14 : 1, i, stream)) != BSLS_OK) return rc;
+        const int k1 = fuse == 2 ? BSLS_STAGE_K1_PARTIAL_INITED : BSLS_STAGE_K1_PARTIAL;
+        if ((rc = bsls_bb_stage(p, k1, i, stream)) != BSLS_OK) return rc;
         if (comm && (rc = comm_sum(c, p->r, (size_t)p->m, st, p->r_fx > 0.0)) != BSLS_OK)
             return rc;
-        if (!fuse && (rc = bsls_bb_stage(p, 9, i, stream)) != BSLS_OK) return rc;
+        if (!fuse && (rc = bsls_bb_stage(p, BSLS_STAGE_R_FINISH, i, stream)) != BSLS_OK) return rc;
     }
-    if (count > 0 && fuse) return bsls_bb_stage(p, 9, first_iter + count - 1, stream);
+    if (count > 0 && fuse)
+        return bsls_bb_stage(p, BSLS_STAGE_R_FINISH, first_iter + count - 1, stream);
     return BSLS_OK;
 }
 
@@ -315,7 +319,7 @@ extern "C" int bsls_bb_shard_iterate_parts(const bsls_bb_problem *p, bsls_comm *
             if ((rc = bsls_bb_k2_part(p, i, q, stream)) != BSLS_OK) return rc;
         }
         if (comm && (rc = comm_sum(c, p->scal + BSLS_S_SUMDG, 5, st)) != BSLS_OK) return rc;
-        if ((rc = bsls_bb_stage(p, 15, i, stream)) != BSLS_OK) return rc;
+        if ((rc = bsls_bb_stage(p, BSLS_STAGE_K3_RECORD_INIT, i, stream)) != BSLS_OK) return rc;
         // K1 by the same parts, each part's exchange started behind it
         for (int q = 0; q < nparts; ++q) {
             if ((rc = bsls_bb_k1_rows(p, i, rb_bounds[q], rb_bounds[q + 1], stream)) != BSLS_OK)
@@ -333,7 +337,7 @@ extern "C" int bsls_bb_shard_iterate_parts(const bsls_bb_problem *p, bsls_comm *
     if (count > 0) {
         if (comm)
             for (int q = 0; q < nparts; ++q) BSLS_CHECK(hipStreamWaitEvent(st, c->ev_ar[q], 0));
-        return bsls_bb_stage(p, 9, first_iter + count - 1, stream);
+        return bsls_bb_stage(p, BSLS_STAGE_R_FINISH, first_iter + count - 1, stream);
     }
     return BSLS_OK;
 }

@@ -1188,7 +1188,7 @@ class BBEngine:
             self.x.copy_(self.colv * xin if self.scaled else xin)
             if self.fixed_sums:
                 self.set_x_bound(float(self.x.abs().max().item()))
-            self.stage(7, 0)                       # r = A x0 + (-b), unweighted
+            self.stage(_native.STAGE_K1, 0)        # r = A x0 + (-b), unweighted
             self.target.copy_(self.r)
         if row_weights is not None:
             self.set_row_weights(row_weights)
@@ -1404,7 +1404,7 @@ class BBEngine:
         self.z[0][:self.nz].copy_(z)
         if self.fixed_sums:
             self.set_x_bound(2.0 * float(z.abs().max().item()) * self.colv_max if self.nz else 0.0)
-        self.stage(6, 0)
+        self.stage(_native.STAGE_Z2X, 0)
 
     def apply_A(self, z, alpha=1.0):
         """alpha A N z (DORE's linop with A scaled by alpha, gradient_descent.py:57-63).
@@ -1412,13 +1412,13 @@ class BBEngine:
         and nabla_f only."""
         self._fixed_only_bb('apply_A (DORE)')
         self._x_of(z)
-        self.stage(1, 0)
+        self.stage(_native.STAGE_K1_PARTIAL, 0)
         return self.r * alpha if alpha != 1.0 else self.r.clone()
 
     def apply_AT(self, r, alpha=1.0):
         """alpha N' A' r (DORE's linop_T)."""
         self.load_r(r)
-        self.stage(3, 0)
+        self.stage(_native.STAGE_K2, 0)
         g = self.g[0][:self.nz]
         return g * alpha if alpha != 1.0 else g.clone()
 
@@ -1426,22 +1426,22 @@ class BBEngine:
         """alpha (A N z + target) (DORE scales A and target by alpha); with
         row_weights w the weighted residual, alpha w * (A N z + target)."""
         self._x_of(z)
-        self.stage(7, 0)
+        self.stage(_native.STAGE_K1, 0)
         return self.r * alpha if alpha != 1.0 else self.r.clone()
 
     def f(self, z):
         """0.5 ||A N z + target||^2 (main.py:53), f as K1's finish forms it; with
         row_weights w, 0.5 sum w_i r_i^2 (and held_out() the zero-weight rows')."""
         self._x_of(z)
-        self.stage(7, 0)
+        self.stage(_native.STAGE_K1, 0)
         return float(self.scal[_native.S_FX].item())
 
     def nabla_f(self, z):
         """N' A' (A N z + target) (main.py:54); with row_weights w,
         N' A' (w * (A N z + target))."""
         self._x_of(z)
-        self.stage(7, 0)
-        self.stage(3, 0)
+        self.stage(_native.STAGE_K1, 0)
+        self.stage(_native.STAGE_K2, 0)
         return self.g[0][:self.nz].clone()
 
     def line_search(self):
@@ -1461,7 +1461,7 @@ class BBEngine:
             # (the stage without target is not covered: the general CSR kernel)
             return self.A.matvec(x)
         self.x.copy_(self.colv * x if self.scaled else x)
-        self.stage(1, 0)
+        self.stage(_native.STAGE_K1_PARTIAL, 0)
         return self.r.clone()
 
     def proj(self, z):

@@ -21,7 +21,7 @@ z, g, x.  Per BB iteration:
 and after the last iteration of a call stage 9 (||r||^2, f, stopping test of
 that iteration).  Once the run has stopped, ranks other than 0 write r = 0 and
 rank 0 leaves its r (the final residual) alone, so the all-reduce keeps the
-final residual intact (csrc/bb.hip k1_stopped_rows), and ranks other than 0
+final residual intact (csrc/bb_k1.hpp k1_stopped_rows), and ranks other than 0
 zero their BB sums before the five-sum all-reduce (k2_stopped_sums).  The
 Python loop below and the C++ driver (bsls_bb_shard_iterate) enqueue the same
 stages; the C++ one takes RCCL (RcclComm) or any transport through a callback
@@ -35,6 +35,8 @@ the r all-reduce (within the 1e-6 iterate contract).
 import os
 
 import numpy as np
+
+import _native
 
 
 def partition_blocks(block_sizes, col_weights, world):
@@ -178,8 +180,9 @@ class ShardedBB:
         """r = sum over ranks of A_g x_g (before stage 2)."""
         e = self.e
         if not self._slices or self.all_reduce_async is None:
-            # (stage 14: K1 after stage 15, which may have initialised r)
-            e.stage(14 if (self.fuse == 2 and it > 0) else 1, it)
+            # (K1_PARTIAL_INITED: K1 after K3_RECORD_INIT, which may have initialised r)
+            e.stage(_native.STAGE_K1_PARTIAL_INITED if (self.fuse == 2 and it > 0)
+                    else _native.STAGE_K1_PARTIAL, it)
             self.all_reduce(self._rx())
             return
         works = []
@@ -239,19 +242,18 @@ class ShardedBB:
     def prologue(self):
         e = self.e
         self._fix_r()
-        e.stage(0, 0)
-        e.stage(5, 0)            # z[1] = z0 + 1, x = x0 + N z[1]
+        e.stage(_native.STAGE_RESET, 0)
+        e.stage(_native.STAGE_Z_PLUS_ONE, 0)   # z[1] = z0 + 1, x = x0 + N z[1]
         self.residual(0)         # r(z0 + 1)
-        e.stage(3, 0)            # g_prev = grad(z0 + 1) -> g[0]
-        e.stage(6, 0)            # x = x0 + N z0
+        e.stage(_native.STAGE_K2, 0)           # g_prev = grad(z0 + 1) -> g[0]
+        e.stage(_native.STAGE_Z2X, 0)          # x = x0 + N z0
         self.residual(0)         # r(z0)
-        e.stage(9, 0)            # f(z0)
+        e.stage(_native.STAGE_R_FINISH, 0)     # f(z0)
 
     def iterate(self, first, count):
         e = self.e
         if self.native is not None:
             import ctypes
-            import _native
             from _native import check, stream_handle
             if count > 0 and self.link:
                 import torch
@@ -276,22 +278,26 @@ class ShardedBB:
             return
         for i in range(first, first + count):
             if self.fuse == 2:
-                e.stage(10, i)   # K2 + this rank's slice of ||r||^2
+                e.stage(_native.STAGE_K2_RR_SLICE, i)   # K2 + this rank's slice of ||r||^2
                 self.all_reduce(e.scal[self.SUMS_RR])
-                # K3 after f / the stopping test of iteration i - 1; stage 15
-                # also sets r to target / 0 for stage 14's atomic K1 where the
-                # library folds that in (what bsls_bb_shard_iterate enqueues);
-                # row parts keep stage 13 (each part initialises its rows)
-                e.stage(13 if self._slices else 15, i)
+                # K3 after f / the stopping test of iteration i - 1;
+                # K3_RECORD_INIT also sets r to target / 0 for
+                # K1_PARTIAL_INITED's atomic K1 where the library folds that in
+                # (what bsls_bb_shard_iterate enqueues); row parts keep
+                # K3_RECORD (each part initialises its rows)
+                e.stage(_native.STAGE_K3_RECORD if self._slices
+                        else _native.STAGE_K3_RECORD_INIT, i)
             else:
-                e.stage(8 if self.fuse else 3, i)   # (8: + f / stop test of i - 1)
+                # (K2_R_FINISH: + f / stop test of i - 1)
+                e.stage(_native.STAGE_K2_R_FINISH if self.fuse else _native.STAGE_K2, i)
                 self.all_reduce(e.scal[self.SUMS])
-                e.stage(4, i)
+                e.stage(_native.STAGE_K3, i)
             self.residual(i)
             if not self.fuse:
-                e.stage(9, i)    # f / stopping test of iteration i
+                e.stage(_native.STAGE_R_FINISH, i)    # f / stopping test of iteration i
         if count > 0 and self.fuse:
-            e.stage(9, first + count - 1)   # f / stopping test of the last one
+            # f / stopping test of the last one
+            e.stage(_native.STAGE_R_FINISH, first + count - 1)
 
     def _iterate_link(self, first, count):
         """The link-part pipeline from Python: what bsls_bb_shard_iterate_parts
@@ -305,7 +311,7 @@ class ShardedBB:
                 e.k2_part(i, q)
             self._works = []
             self.all_reduce(e.scal[self.SUMS_RR])
-            e.stage(15, i)
+            e.stage(_native.STAGE_K3_RECORD_INIT, i)
             for q, (rb0, rb1, r0, r1) in enumerate(self._slices):
                 e.k1_rows(i, rb0, rb1)
                 self._works.append(self.all_reduce_async(self._rx()[r0:r1]))
@@ -313,13 +319,12 @@ class ShardedBB:
             for w in self._works:
                 w.wait()
             self._works = []
-            e.stage(9, first + count - 1)
+            e.stage(_native.STAGE_R_FINISH, first + count - 1)
 
 
 def comm_count(handle):
     """bsls_comm_count: the ranks a C-ABI communicator spans."""
     import ctypes
-    import _native
     from _native import check
     n = ctypes.c_int(0)
     check(_native.lib().bsls_comm_count(handle, ctypes.byref(n)), 'bsls_comm_count')
@@ -355,7 +360,6 @@ class CallbackComm:
 
     def __init__(self, all_reduce, views=None, rank=None, world=None, engine=None):
         import ctypes
-        import _native
         from _native import check
         self.rank = _shard_rank(rank)
         self.world = int(world) if world is not None else _world_size()
@@ -397,7 +401,6 @@ class CallbackComm:
         return comm_count(self.handle)
 
     def close(self):
-        import _native
         if self.handle is not None:
             _native.lib().bsls_comm_destroy(self.handle)
             self.handle = None
@@ -410,7 +413,6 @@ class ModelComm:
 
     def __init__(self, world, rank, fixed_us=0.0, us_per_mb=0.0):
         import ctypes
-        import _native
         from _native import check
         self.world, self.rank = int(world), int(rank)
         h = ctypes.c_void_p()
@@ -420,7 +422,6 @@ class ModelComm:
         self.handle = h
 
     def close(self):
-        import _native
         if self.handle is not None:
             _native.lib().bsls_comm_destroy(self.handle)
             self.handle = None
@@ -439,7 +440,6 @@ class RcclComm:
         import ctypes
         import torch
         import torch.distributed as dist
-        import _native
         from _native import check
         L = _native.lib()
         nb = int(L.bsls_comm_id_bytes())
@@ -464,13 +464,11 @@ class RcclComm:
 
     def all_reduce(self, t):
         """In-place sum of a float64 device tensor over the ranks (current stream)."""
-        import _native
         from _native import check, ptr, stream_handle
         check(_native.lib().bsls_comm_all_reduce(self.handle, ptr(t), t.numel(),
                                                  stream_handle()), 'bsls_comm_all_reduce')
 
     def close(self):
-        import _native
         if self.handle is not None:
             _native.lib().bsls_comm_destroy(self.handle)
             self.handle = None

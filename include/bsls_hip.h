@@ -491,35 +491,57 @@ int bsls_bb_prologue(const bsls_bb_problem *p, void *stream);
 /* Enqueue iterations first_iter .. first_iter+count-1 (first_iter >= 1); after
  * iteration i the iterate is z[i & 1] unless the run stopped (scal[ZBUF]). */
 int bsls_bb_iterate(const bsls_bb_problem *p, int64_t first_iter, int64_t count, void *stream);
-/* The building blocks, for multi-GPU column sharding where RCCL all-reduces sit
- * between them (A_g = the rank's block-aligned column slice):
- *   0  reset scal[] and the reduction tickets
- *   1  r = A_g x_g            (partial residual; all-reduce r afterwards); with
- *      shard_role 1 r = A_g x_g + target (the sum over ranks is the residual)
- *   2  r += target, ||r||^2, f, stopping test of iteration `iter` (iter 0: none)
- *   3  g = N'A'r -> g[iter & 1]; iter > 0 also dg and the four BB sums into
- *      scal[SUMDG..GG] (all-reduce those four afterwards)
- *   4  t from the sums, z[iter&1] = clip01(PAVA(z - t g)), x = N z, dz for stage 3
- *   5  z[1] = z[0] + 1, x = N z[1]           (prologue)
- *   6  x = N z[0]                             (prologue)
- *   7  single GCD: r = A x + target, ||r||^2, f, stopping test (= 1 then 2 fused)
- *   8  stage 3 (iter >= 1) with stage 9 of iteration iter - 1 folded into it:
- *      every workgroup also sums its slice of r^2, and the last one records f
- *      and runs the stopping test of iter - 1 (with the all-reduced g.g of
- *      iter - 1) before it stores iteration iter's four sums
- *   9  ||r||^2, f, stopping test of iteration `iter` (r already the residual)
- *  10  stage 3 (iter >= 1) with this rank's share of ||r||^2 (rows [rr_lo,
- *      rr_hi)) into scal[RR] beside the four sums, iteration iter - 1's sums
- *      kept in scal[PSUMDG..PGG]; all-reduce scal[SUMDG..RR] (5) afterwards
- *  12  f and the stopping test of iteration iter - 1 from those (after the
- *      all-reduce, before stage 4)
- *  13  stage 12 folded into stage 4 (K3's workgroups all decide the stop of
- *      iter - 1 from the same scal values, workgroup 0 records it)
- *  15  stage 13 that also sets r to target (shard_role 1) / 0 for stage 14
- *      when K1 adds its column groups' sums by atomics (a column shard's
- *      dealt K1 with several groups); otherwise stage 13
- *  14  stage 1 after stage 15 (without its own r initialisation then)
- * One iteration i >= 1 = 3, [allreduce sums], 4, 1, [allreduce r], 2; on one GCD
+/* The building blocks (bsls_bb_stage's `stage`), for multi-GPU column sharding
+ * where RCCL all-reduces sit between them (A_g = the rank's block-aligned
+ * column slice).  The values are part of the ABI; 11 is unassigned and, as
+ * everything outside 0..15, BSLS_E_ARG. */
+enum bsls_stage {
+    /* reset scal[] and the reduction tickets */
+    BSLS_STAGE_RESET = 0,
+    /* r = A_g x_g (partial residual; all-reduce r afterwards); with
+     * shard_role 1 r = A_g x_g + target (the sum over ranks is the residual) */
+    BSLS_STAGE_K1_PARTIAL = 1,
+    /* r += target, ||r||^2, f, stopping test of iteration `iter` (iter 0: none) */
+    BSLS_STAGE_R_FINISH_TARGET = 2,
+    /* g = N'A'r -> g[iter & 1]; iter > 0 also dg and the four BB sums into
+     * scal[SUMDG..GG] (all-reduce those four afterwards) */
+    BSLS_STAGE_K2 = 3,
+    /* t from the sums, z[iter&1] = clip01(PAVA(z - t g)), x = N z, dz for
+     * BSLS_STAGE_K2 (iter >= 1) */
+    BSLS_STAGE_K3 = 4,
+    /* z[1] = z[0] + 1, x = N z[1]           (prologue) */
+    BSLS_STAGE_Z_PLUS_ONE = 5,
+    /* x = N z[0]                             (prologue) */
+    BSLS_STAGE_Z2X = 6,
+    /* single GCD: r = A x + target, ||r||^2, f, stopping test (= 1 then 2 fused) */
+    BSLS_STAGE_K1 = 7,
+    /* BSLS_STAGE_K2 (iter >= 1) with BSLS_STAGE_R_FINISH of iteration iter - 1
+     * folded into it: every workgroup also sums its slice of r^2, and the last
+     * one records f and runs the stopping test of iter - 1 (with the
+     * all-reduced g.g of iter - 1) before it stores iteration iter's four sums */
+    BSLS_STAGE_K2_R_FINISH = 8,
+    /* ||r||^2, f, stopping test of iteration `iter` (r already the residual) */
+    BSLS_STAGE_R_FINISH = 9,
+    /* BSLS_STAGE_K2 (iter >= 1) with this rank's share of ||r||^2 (rows [rr_lo,
+     * rr_hi)) into scal[RR] beside the four sums, iteration iter - 1's sums
+     * kept in scal[PSUMDG..PGG]; all-reduce scal[SUMDG..RR] (5) afterwards */
+    BSLS_STAGE_K2_RR_SLICE = 10,
+    /* f and the stopping test of iteration iter - 1 from those (iter >= 1;
+     * after the all-reduce, before BSLS_STAGE_K3) */
+    BSLS_STAGE_RECORD = 12,
+    /* BSLS_STAGE_RECORD folded into BSLS_STAGE_K3 (K3's workgroups all decide
+     * the stop of iter - 1 from the same scal values, workgroup 0 records it) */
+    BSLS_STAGE_K3_RECORD = 13,
+    /* BSLS_STAGE_K1_PARTIAL (iter >= 1) after BSLS_STAGE_K3_RECORD_INIT
+     * (without its own r initialisation then) */
+    BSLS_STAGE_K1_PARTIAL_INITED = 14,
+    /* BSLS_STAGE_K3_RECORD that also sets r to target (shard_role 1) / 0 for
+     * BSLS_STAGE_K1_PARTIAL_INITED when K1 adds its column groups' sums by
+     * atomics (a column shard's dealt K1 with several groups); otherwise
+     * BSLS_STAGE_K3_RECORD */
+    BSLS_STAGE_K3_RECORD_INIT = 15
+};
+/* One iteration i >= 1 = 3, [allreduce sums], 4, 1, [allreduce r], 2; on one GCD
  * bsls_bb_iterate runs 3, 4, 7.  The column-sharded driver (distributed.py,
  * shard_role 1 / 2) runs 8, [allreduce sums], 4, 1, [allreduce r] per
  * iteration and 9 after the last one (fuse 1), or the sliced form 10,

@@ -74,13 +74,37 @@ def _c_layout(tmp_path, struct, fields):
 @pytest.mark.parametrize('struct,cls', [('bsls_bb_problem', 'BBProblem'), ('bsls_panels', 'Panels'),
                                         ('bsls_xbb_problem', 'XBBProblem'), ('bsls_csr', 'CSR'),
                                         ('bsls_tiles', 'Tiles'), ('bsls_dore_state', 'DoreState'),
-                                        ('bsls_lsq_op', 'LsqOp')])
+                                        ('bsls_lsq_op', 'LsqOp'),
+                                        ('bsls_bbm_problem', 'BBMProblem'),
+                                        ('bsls_ls_state', 'LsState')])
 def test_struct_layout_matches_header(native, tmp_path, struct, cls):
     C = getattr(native, cls)
     names = [f[0] for f in C._fields_]
     want = _c_layout(tmp_path, struct, names)
     got = [ctypes.sizeof(C)] + [getattr(C, f).offset for f in names]
     assert got == want
+
+
+def test_stage_ids_match_header(native, tmp_path):
+    """Every enumerator of the header's enum bsls_stage, as the C compiler
+    values it, has its _native.STAGE_* twin and the other way round; the ids
+    are 0..10 and 12..15 (11 stays unassigned)."""
+    import re
+    hdr = open(os.path.join(ROOT, 'include', 'bsls_hip.h')).read()
+    enum = re.search(r'enum bsls_stage \{(.*?)\};', hdr, re.S).group(1)
+    names = re.findall(r'^\s*(BSLS_STAGE_\w+)\s*=', enum, re.M)
+    src = tmp_path / 'stages.c'
+    src.write_text('#include <stdio.h>\n#include "bsls_hip.h"\n'
+                   'int main(void){%s return 0;}\n'
+                   % ''.join('printf("%%d\\n", (int)%s);' % n for n in names))
+    exe = tmp_path / 'stages'
+    subprocess.run(['gcc', '-I', os.path.join(ROOT, 'include'), str(src), '-o', str(exe)],
+                   check=True)
+    out = subprocess.run([str(exe)], check=True, capture_output=True, text=True).stdout.split()
+    c_ids = {n[len('BSLS_'):]: int(v) for n, v in zip(names, out)}
+    py_ids = {k: v for k, v in vars(native).items() if k.startswith('STAGE_')}
+    assert c_ids == py_ids
+    assert sorted(c_ids.values()) == list(range(11)) + list(range(12, 16))
 
 
 def test_panel_limits_match_header(native):

@@ -432,3 +432,39 @@ def test_sy_dr_retired(cuda, shard100k):
     eng.P.sy_dr = 0
     eng.prologue()
     eng.iterate(1, 3)
+
+
+def test_stage_refusals(cuda):
+    """bsls_bb_stage's table of what a stage asks for (csrc/bb.hip
+    STAGE_RULES): on a plain engine, one with fixed_sums and one with row
+    weights, every stage id the problem's kind does not cover, the unassigned
+    11 and the ids outside 0..15 are BSLS_E_ARG, and so are the iterating
+    stages at iter = 0 -- all before any launch; one covered stage per engine
+    goes through."""
+    import torch
+    import _native
+    from device import BBEngine
+    from synthetic import make_shard, add_noise
+    sh = make_shard(5_000, 250, 500, per_col=16)
+    b = add_noise(sh['Ax'], 0.02)
+    L = _native.lib()
+    every = set(range(-1, 17))
+    covered = {'plain': set(range(11)) | {12, 13, 14, 15},
+               'fixed': {0, 3, 4, 5, 6, 7, 9},
+               'weights': {0, 1, 3, 4, 5, 6, 7}}
+    engines = {'plain': {}, 'fixed': {'fixed_sums': True}, 'weights': {'row_weights': np.ones(500)}}
+    for kind, kw in engines.items():
+        eng = BBEngine(sh['A'], b, sh['block_sizes'], options={'max_iter': 5, 'opt_tol': 1e-30},
+                       **kw)
+        assert bool(eng.P.fx_sums) == (kind == 'fixed') and bool(eng.P.roww) == (kind == 'weights')
+        eng.set_z0(np.zeros(eng.nz))
+        eng.prologue()
+        for stage in sorted(every - covered[kind]):
+            rc = L.bsls_bb_stage(eng.P, stage, 1, _native.stream_handle())
+            assert rc == _native.BSLS_E_ARG, (kind, stage, rc)
+        if kind == 'plain':
+            for stage in (4, 8, 10, 12, 13, 14, 15):
+                rc = L.bsls_bb_stage(eng.P, stage, 0, _native.stream_handle())
+                assert rc == _native.BSLS_E_ARG, (kind, stage, rc)
+        assert L.bsls_bb_stage(eng.P, 6, 0, _native.stream_handle()) == _native.BSLS_OK
+        torch.cuda.synchronize()
