@@ -37,6 +37,7 @@ import os
 import numpy as np
 
 import _native
+from dev_images import row_parts          # (a planner; still exported from here)
 
 
 def partition_blocks(block_sizes, col_weights, world):
@@ -59,12 +60,6 @@ def partition_blocks(block_sizes, col_weights, world):
         bounds.append(b)
     bounds.append(p)
     return np.array(bounds, dtype=np.int64)
-
-
-def row_parts(nblocks, parts):
-    """parts + 1 row-block bounds splitting K1's row blocks into `parts` runs."""
-    parts = max(1, min(int(parts), int(nblocks)))
-    return [int(v) for v in np.round(np.linspace(0, nblocks, parts + 1)).astype(np.int64)]
 
 
 def _world_size():

@@ -380,13 +380,14 @@ def test_iso_plan_cache_by_content(monkeypatch):
     another length make a new one, and changing the caller's array in place
     after caching does not alias the cached entry (the cache keeps a copy)."""
     import device
+    import dev_blocks                 # where iso_plan resolves what is patched here
     made = []
 
     class Stub:
         def __init__(self, st, n):
             made.append((st.copy(), n))
-    monkeypatch.setattr(device, 'IsoPlan', Stub)
-    monkeypatch.setattr(device, '_iso_plans', {})
+    monkeypatch.setattr(dev_blocks, 'IsoPlan', Stub)
+    monkeypatch.setattr(dev_blocks, '_iso_plans', {})
     a = np.array([0, 3, 7, 12], dtype=np.int64)
     p1 = device.iso_plan(a, 20)
     assert device.iso_plan(a.copy(), 20) is p1
@@ -402,10 +403,10 @@ def test_iso_plan_cache_by_content(monkeypatch):
     assert device.iso_plan(np.array([0, 3, 7, 12]), 20) is p1
     # a plan's arrays live on one GPU: the same layout on another device is
     # planned again, and the first device still finds its own
-    monkeypatch.setattr(device, '_cur_dev', lambda: 5)
+    monkeypatch.setattr(dev_blocks, '_cur_dev', lambda: 5)
     p5 = device.iso_plan(np.array([0, 3, 7, 12]), 20)
     assert p5 is not p1 and len(made) == 5
-    monkeypatch.setattr(device, '_cur_dev', lambda: -1)
+    monkeypatch.setattr(dev_blocks, '_cur_dev', lambda: -1)
     assert device.iso_plan(np.array([0, 3, 7, 12]), 20) is p1
 
 

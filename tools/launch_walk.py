@@ -14,6 +14,11 @@ difference, or when one of the unit's kernels was never dispatched).
 The problems are those of tests/test_gpu_row_weights.py (a 5 000-column
 incidence in 250 blocks; K1 on tiles of 192 rows in 1 / 4 / 10 column groups
 or on panels) at m = 500 and 501 rows, so bb_k1_sum runs in both widths.
+After the BB unit the walk enqueues what else the host layer sequences, on
+the same problem and the small x-space rig of tests/test_gpu_xbb_rounds.py:
+BatchBB at R = 1, 3 and 8, DeviceLSQ on every image form, XBBEngine with and
+without L-BFGS, IsoPlan.apply in both modes, and BBEngine.solve /
+BatchBB.solve over poll windows that the record boundaries cut.
 """
 import argparse
 import csv
@@ -33,11 +38,11 @@ UNIT = ('bb_k1', 'bb_k1t', 'bb_k1_sum', 'bb_k1_init', 'bb_r_finish', 'bb_k2', 'b
 OPTS = {'max_iter': 50, 'opt_tol': 1e-30}
 
 
-def engine(m, form, sizes=None, **kw):
+def engine(m, form, sizes=None, options=OPTS, **kw):
     import test_gpu_row_weights as rw
     from device import BBEngine
     sh, b = rw.small(m)
-    return BBEngine(sh['A'], b, sh['block_sizes'] if sizes is None else sizes, options=OPTS,
+    return BBEngine(sh['A'], b, sh['block_sizes'] if sizes is None else sizes, options=options,
                     **dict(rw.FORMS[form], **kw))
 
 
@@ -171,6 +176,70 @@ def walk():
         eng.line_search().search(x, d.contiguous(), gx, fx)
         torch.cuda.synchronize()
 
+    walk_host_layer()
+
+
+def walk_host_layer():
+    """What the host layer launches beside the BB unit: the batched engine,
+    the x-space operator pair and engine, the isotonic plan, and the solve
+    loops' poll windows."""
+    import numpy as np
+    import torch
+    import test_gpu_row_weights as rw
+    import test_gpu_xbb_rounds as xr
+    from device import BatchBB, BlockLayout, DeviceLSQ
+
+    m = 500
+    sh, b = rw.small(m)
+
+    def batch(R, weighted, options=OPTS):
+        wts = [rw.mixed_weights(m) if weighted and j == 0 else None for j in range(R)]
+        return BatchBB(sh['A'], [b * (1.0 + 0.125 * j) for j in range(R)], sh['block_sizes'],
+                       row_weights=wts, options=options)
+
+    # the batched engine at every interleave width, one problem weighted or none
+    for R in (1, 3, 8):
+        for weighted in (False, True):
+            eng = batch(R, weighted)
+            eng.set_z0(None)
+            eng.prologue()
+            eng.iterate(1, 2)
+            torch.cuda.synchronize()
+
+    # the x-space operator pair on each image form: one residual, one gradient
+    A = xr.problem('Podd')[0].tocsr()
+    for k1, k2 in (('panels', 'panels'), ('tiles', 'panels'), ('tiles_fixed', 'panels'),
+                   ('panels', 'tiles'), ('tiles', 'tiles'), ('tiles_fixed', 'tiles')):
+        op = DeviceLSQ(A, A.T.tocsr(), k1=k1, k2=k2)
+        x = torch.full((op.n,), 0.5, dtype=torch.float64, device='cuda')
+        r = torch.empty(op.m, dtype=torch.float64, device='cuda')
+        g = torch.empty(op.n, dtype=torch.float64, device='cuda')
+        sq = torch.zeros(1, dtype=torch.float64, device='cuda')
+        op.residual(x, r, sq=sq)
+        op.gradient(r, g)
+        torch.cuda.synchronize()
+
+    # the x-space engine: BB rounds and L-BFGS rounds (3 corrections)
+    for C in (0, 3):
+        R = xr.Rig('Podd', 'tiles_fixed', C=C)
+        R.start(R.x_start, R.params())
+        R.eng.rounds(2)
+        R.eng.rounds(2)
+        torch.cuda.synchronize()
+
+    # the isotonic plan of the z-layout, bit-exact and prefix-sum
+    lay = BlockLayout(sh['block_sizes'])
+    y = torch.from_numpy(np.random.RandomState(11).rand(lay.nz)).cuda()
+    for fast in (False, True):
+        lay.iso_plan().apply(y.clone(), fast=fast)
+    torch.cuda.synchronize()
+
+    # the solve loops: windows of 2 cut at the record boundaries 3 and 6, then 7
+    opts = {'max_iter': 7, 'opt_tol': 1e-30}
+    engine(m, 'tiles4', options=opts, deterministic=True).solve(record_every=3, poll=2)
+    batch(3, True, options=opts).solve(record_every=3, poll=2)
+    torch.cuda.synchronize()
+
 
 def trace_rows(path):
     rows = list(csv.DictReader(open(path)))
@@ -182,7 +251,8 @@ def trace_rows(path):
 
 def template_of(name):
     """bb_k1t of `void bsls::bb_k1t<1, true, ...>(...)`; None outside the unit."""
-    base = name.split('(')[0].split('<')[0].split()[-1].split('::')[-1]
+    words = name.replace('(anonymous namespace)::', '').split('(')[0].split('<')[0].split()
+    base = words[-1].split('::')[-1] if words else None
     return base if base in UNIT else None
 
 
