@@ -86,6 +86,9 @@ def solve_engine(engine, z0, scale, target, record_every=5, log=None, options=No
     import torch
     import _native
     from _native import ptr, stream_handle, check
+    if getattr(engine, 'reg_lambda', 0.0):
+        raise ValueError('DORE is not covered by a regulariser (BB only): '
+                         'set_regulariser(0) first')
     start = log(0, z0, 0)
     if options and 'max_iter' in options:
         i = options['max_iter']

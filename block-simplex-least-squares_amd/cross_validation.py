@@ -5,8 +5,11 @@ A[train, :], b[train], runs z-space BB on them and scores the fit on the
 held-out links.  Here a fold is a 0/1 vector of per-link weights on ONE device
 engine (device.BBEngine.set_row_weights): the matrix images are the whole
 problem's, built once, the weights act in K1's row finish, and the same pass
-that forms f over the train rows sums the held-out error.  Label-grouped folds
-and the regularised objectives of the reference are not carried.
+that forms f over the train rows sums the held-out error.  The reference's
+label-grouped folds are label_masks; its regularised objective (reg = 'L2',
+with or without weights, CrossValidation.py:140-148) is the engine's
+set_regulariser, and kfold_path picks lambda over every (lambda, fold) on one
+engine.  Loading the reference's travel-time and label pickles is not carried.
 """
 import logging
 import time
@@ -39,6 +42,51 @@ def kfold_masks(m, k, shuffle=False, seed=0):
     return masks
 
 
+def label_masks(labels, k=None):
+    """Folds that keep the rows of one label together, as float64 0/1 vectors
+    (0 = held out; every row in exactly one fold).  k=None: one fold per
+    distinct label, in sorted label order -- sklearn's LeaveOneLabelOut as the
+    reference calls it for taz_ids / city_ids (CrossValidation.py:75-91).  An
+    int k: KFold(k) over the sorted distinct labels, the first (labels % k)
+    folds one label longer (the street_names form, :92-110)."""
+    labels = np.asarray(labels).reshape(-1)
+    if labels.size == 0:
+        raise ValueError('label_masks needs one label per row')
+    uniq, inv = np.unique(labels, return_inverse=True)
+    nl = int(uniq.size)
+    if k is None:
+        if nl < 2:
+            raise ValueError('leave-one-label-out needs at least 2 distinct labels')
+        groups = [[j] for j in range(nl)]
+    else:
+        if isinstance(k, bool) or not isinstance(k, (int, np.integer)) or k < 2:
+            raise ValueError('label folds need an int k >= 2 (got %r)' % (k,))
+        if k > nl:
+            raise ValueError('more folds (%d) than distinct labels (%d)' % (k, nl))
+        sizes = np.full(int(k), nl // int(k), dtype=np.int64)
+        sizes[:nl % int(k)] += 1
+        ends = np.cumsum(sizes)
+        groups = [list(range(lo, hi)) for lo, hi in zip(ends - sizes, ends)]
+    masks = []
+    for grp in groups:
+        w = np.ones(labels.size, dtype=np.float64)
+        w[np.isin(inv.reshape(-1), grp)] = 0.0
+        masks.append(w)
+    return masks
+
+
+def _fold_masks(m, k, shuffle, seed, masks):
+    """kfold's folds: the caller's masks (each m values, 0 = held out), or
+    kfold_masks(m, k)."""
+    if masks is None:
+        return kfold_masks(m, k, shuffle=shuffle, seed=seed)
+    from device import row_weights_check
+    masks = [row_weights_check(w, m) for w in masks]
+    if not masks:
+        raise ValueError('masks is empty')
+    return masks
+
+
 class _StopText(logging.Handler):
     """The message solvers.stopping logs when it ends a host run."""
 
@@ -52,7 +100,7 @@ class _StopText(logging.Handler):
             self.text = msg
 
 
-def _kfold_cpu(A, b, x0, N, block_sizes, masks, options):
+def _kfold_cpu(A, b, x0, N, block_sizes, masks, options, reg_lambda=0.0, reg_weights=None):
     from main import solve_in_z_cpu
     out = []
     target = A.dot(x0) - b
@@ -64,7 +112,8 @@ def _kfold_cpu(A, b, x0, N, block_sizes, masks, options):
         t0 = time.time()
         try:
             iters, _, states = solve_in_z_cpu(A, b, x0, N, block_sizes, 'BB', options=options,
-                                              row_weights=w)
+                                              row_weights=w, reg_lambda=reg_lambda,
+                                              reg_weights=reg_weights)
         finally:
             root.removeHandler(catch)
         dt = time.time() - t0
@@ -76,8 +125,13 @@ def _kfold_cpu(A, b, x0, N, block_sizes, masks, options):
             # (BB.py:22's exact-zero sum(delta_g) exit prints the same text
             # as the stopping rule's last test)
             stop = catch.text or 'Exiting... no change in gradient'
+        f_train = 0.5 * float(np.sum(w * r * r))
+        if reg_lambda:
+            d = np.ones(A.shape[1]) if reg_weights is None else np.asarray(reg_weights)
+            xh = N.dot(z) + x0
+            f_train += 0.5 * float(np.sum(reg_lambda * d * d * xh * xh))
         out.append({'iters': int(iters[-1]), 'stop': stop,
-                    'f_train': 0.5 * float(np.sum(w * r * r)),
+                    'f_train': f_train,
                     'held_out': 0.5 * float(np.sum(r[w == 0.0] ** 2)),
                     'z': z, 'seconds': dt})
     return out
@@ -114,7 +168,7 @@ def _kfold_batch(A, b, x0, block_sizes, masks, options, batch):
 
 
 def kfold(A, b, x0, N, block_sizes, k, options=None, device='gpu', engine=None, shuffle=False,
-          seed=0, deterministic=None, batch=None):
+          seed=0, deterministic=None, batch=None, reg_lambda=0.0, reg_weights=None, masks=None):
     """K-fold cross-validation of the z-space BB fit: fold i holds out the rows
     where kfold_masks(m, k)[i] is 0, fits the rest from z0 = x2z(x0) and scores
     0.5 ||A_test x - b_test||^2 on the held-out rows.  Returns one dict per
@@ -133,16 +187,29 @@ def kfold(A, b, x0, N, block_sizes, k, options=None, device='gpu', engine=None, 
     device='cpu' accepts and ignores it.  Measured on C3 (profiles/batch_bb_C3.txt): the batch costs
     147.9 us per iteration and problem at batch = 8 (342.6 at 1) against the
     fused engine's 73.5 us, so the sequential path is the faster one and stays
-    the default; batch buys lockstep fits that repeat bit for bit."""
+    the default; batch buys lockstep fits that repeat bit for bit.
+
+    reg_lambda / reg_weights: the reference's weighted L2 regulariser on every
+    fold's fit (BBEngine.set_regulariser; main.solve_in_z_cpu on 'cpu');
+    f_train is then the regularised objective, held_out stays the plain error
+    of the held-out rows.  Not with batch (ValueError).  masks: the folds as
+    0/1 vectors instead of kfold_masks(m, k) -- label_masks' -- k is then not
+    used."""
+    from device import reg_lambda_check, reg_weights_check
+    reg_lambda = reg_lambda_check(reg_lambda)
+    reg_weights = reg_weights_check(reg_weights, A.shape[1])
+    if batch is not None and reg_lambda:
+        raise ValueError('batch does not cover a regulariser: run the folds on one engine '
+                         '(batch=None)')
     if batch is not None:
         if isinstance(batch, bool) or not isinstance(batch, (int, np.integer)) \
                 or not 1 <= batch <= 8:
             raise ValueError('batch must be None or an int in 1..8 (got %r)' % (batch,))
     from bsls_utils import x2z
     block_sizes = np.asarray(block_sizes)
-    masks = kfold_masks(A.shape[0], k, shuffle=shuffle, seed=seed)
+    masks = _fold_masks(A.shape[0], k, shuffle, seed, masks)
     if device == 'cpu':
-        return _kfold_cpu(A, b, x0, N, block_sizes, masks, options)
+        return _kfold_cpu(A, b, x0, N, block_sizes, masks, options, reg_lambda, reg_weights)
     if device != 'gpu':
         raise ValueError("device must be 'gpu' or 'cpu' (got %r)" % (device,))
     if batch is not None:
@@ -156,12 +223,15 @@ def kfold(A, b, x0, N, block_sizes, k, options=None, device='gpu', engine=None, 
                            row_weights=masks[0])
     before = eng.row_weights
     keep = (eng.P.max_iter, eng.P.opt_tol)
+    reg_before, d_before = eng.reg_lambda, eng.reg_d
     if options is not None:
         eng.P.max_iter = int(options.get('max_iter', 300000))
         eng.P.opt_tol = float(options.get('opt_tol', 1e-6))
     z0 = x2z(x0, block_sizes)
     out = []
     try:
+        if reg_lambda or reg_before:
+            eng.set_regulariser(reg_lambda, reg_weights)
         for w in masks:
             t0 = time.time()
             eng.set_row_weights(w)
@@ -175,4 +245,35 @@ def kfold(A, b, x0, N, block_sizes, k, options=None, device='gpu', engine=None, 
     finally:
         eng.set_row_weights(before)
         eng.P.max_iter, eng.P.opt_tol = keep
+        if reg_lambda or reg_before or eng.reg_d is not d_before:
+            # an engine passed in gets its own lambda and d back
+            eng.reg_d = d_before
+            eng.set_regulariser(reg_before)
     return out
+
+
+def kfold_path(A, b, x0, N, block_sizes, k, lambdas, reg_weights=None, options=None,
+               device='gpu', engine=None, shuffle=False, seed=0, deterministic=None, masks=None):
+    """Choose lambda by cross-validation: kfold(..., reg_lambda=lam) for every
+    lam of `lambdas`, all (lambda, fold) fits on ONE engine on 'gpu' (`engine`
+    or one built here; changing lambda is one elementwise device op).  Returns
+    {'lambdas', 'folds' (per lambda the fold dicts), 'held_out' (per lambda the
+    mean held-out error), 'best' (the arg-min lambda, the first on a tie),
+    'best_index'}."""
+    from device import reg_lambda_check
+    lams = [reg_lambda_check(l) for l in lambdas]
+    if not lams:
+        raise ValueError('kfold_path needs at least one lambda')
+    block_sizes = np.asarray(block_sizes)
+    masks = _fold_masks(A.shape[0], k, shuffle, seed, masks)
+    eng = engine
+    if device == 'gpu' and eng is None:
+        from main import build_engine
+        eng = build_engine(A, b, x0, block_sizes, options=options, deterministic=deterministic,
+                           row_weights=masks[0], reg_weights=reg_weights)
+    folds = [kfold(A, b, x0, N, block_sizes, k, options=options, device=device, engine=eng,
+                   reg_lambda=lam, reg_weights=reg_weights, masks=masks) for lam in lams]
+    held = [float(np.mean([f['held_out'] for f in fs])) for fs in folds]
+    best = int(np.argmin(held))
+    return {'lambdas': lams, 'folds': folds, 'held_out': held, 'best': lams[best],
+            'best_index': best}

@@ -37,6 +37,10 @@
 // the 1e-16 level -- unless bsls_bb_problem.fx_sums (BBEngine(fixed_sums=True))
 // has them summed as integers in fixed point, which is order-free.
 // Scalars live in device memory (scal[]); the host only polls them.
+// bsls_bb_problem.reg_w adds the reference's weighted L2 regulariser
+// (CrossValidation.py:140-148): a fourth kernel between K3 and K1 (bb_reg.hpp)
+// leaves N'(w o (N z + x0)) for the next K2's epilogue and sum w (N z + x0)^2
+// for the f that K1's finish records.
 #include "pava.hpp"
 #include "pava_long.hpp"
 #include "pava_wave.hpp"
@@ -51,6 +55,7 @@
 #include "bb_k1.hpp"
 #include "bb_k2.hpp"
 #include "bb_k3.hpp"
+#include "bb_reg.hpp"
 #include "bb_launch.hpp"
 
 using namespace bsls;
@@ -99,28 +104,30 @@ extern "C" int bsls_bb_rmax_slots(void) { return RMAX_SLOTS; }
 // stage id (include/bsls_hip.h bsls_stage); an id outside the table, or the
 // unassigned 11, is BSLS_E_ARG.  fx_sums: the single-GCD stages only.  roww:
 // the same without R_FINISH (||r||^2 of the stored w o is not the objective)
-// and with K1_PARTIAL, which without target stays the unweighted A x.  A new stage gets a row: it
+// and with K1_PARTIAL, which without target stays the unweighted A x.  reg
+// (reg_w): the single-GCD stages, K1_PARTIAL included (no f, no gradient: the
+// plain A x), without the stages that finish r apart from K1's walk.  A new stage gets a row: it
 // inherits nothing.
 struct StageRule {
-    bool known, needs_iter, fx_sums, roww;   // needs_iter: iter >= 1
+    bool known, needs_iter, fx_sums, roww, reg;   // needs_iter: iter >= 1
 };
 static const StageRule STAGE_RULES[] = {
-    /* BSLS_STAGE_RESET             0 */ {true, false, true, true},
-    /* BSLS_STAGE_K1_PARTIAL        1 */ {true, false, false, true},
-    /* BSLS_STAGE_R_FINISH_TARGET   2 */ {true, false, false, false},
-    /* BSLS_STAGE_K2                3 */ {true, false, true, true},
-    /* BSLS_STAGE_K3                4 */ {true, true, true, true},
-    /* BSLS_STAGE_Z_PLUS_ONE        5 */ {true, false, true, true},
-    /* BSLS_STAGE_Z2X               6 */ {true, false, true, true},
-    /* BSLS_STAGE_K1                7 */ {true, false, true, true},
-    /* BSLS_STAGE_K2_R_FINISH       8 */ {true, true, false, false},
-    /* BSLS_STAGE_R_FINISH          9 */ {true, false, true, false},
-    /* BSLS_STAGE_K2_RR_SLICE      10 */ {true, true, false, false},
-    /* unassigned                  11 */ {false, false, false, false},
-    /* BSLS_STAGE_RECORD           12 */ {true, true, false, false},
-    /* BSLS_STAGE_K3_RECORD        13 */ {true, true, false, false},
-    /* BSLS_STAGE_K1_PARTIAL_INITED 14 */ {true, true, false, false},
-    /* BSLS_STAGE_K3_RECORD_INIT   15 */ {true, true, false, false},
+    /* BSLS_STAGE_RESET             0 */ {true, false, true, true, true},
+    /* BSLS_STAGE_K1_PARTIAL        1 */ {true, false, false, true, true},
+    /* BSLS_STAGE_R_FINISH_TARGET   2 */ {true, false, false, false, false},
+    /* BSLS_STAGE_K2                3 */ {true, false, true, true, true},
+    /* BSLS_STAGE_K3                4 */ {true, true, true, true, true},
+    /* BSLS_STAGE_Z_PLUS_ONE        5 */ {true, false, true, true, true},
+    /* BSLS_STAGE_Z2X               6 */ {true, false, true, true, true},
+    /* BSLS_STAGE_K1                7 */ {true, false, true, true, true},
+    /* BSLS_STAGE_K2_R_FINISH       8 */ {true, true, false, false, false},
+    /* BSLS_STAGE_R_FINISH          9 */ {true, false, true, false, false},
+    /* BSLS_STAGE_K2_RR_SLICE      10 */ {true, true, false, false, false},
+    /* unassigned                  11 */ {false, false, false, false, false},
+    /* BSLS_STAGE_RECORD           12 */ {true, true, false, false, false},
+    /* BSLS_STAGE_K3_RECORD        13 */ {true, true, false, false, false},
+    /* BSLS_STAGE_K1_PARTIAL_INITED 14 */ {true, true, false, false, false},
+    /* BSLS_STAGE_K3_RECORD_INIT   15 */ {true, true, false, false, false},
 };
 static_assert(sizeof(STAGE_RULES) / sizeof(STAGE_RULES[0]) == BSLS_STAGE_K3_RECORD_INIT + 1,
               "one row per stage id");
@@ -135,7 +142,7 @@ extern "C" int bsls_bb_stage(const bsls_bb_problem *p, int stage, int64_t iter, 
     if (stage < 0 || stage > BSLS_STAGE_K3_RECORD_INIT) return BSLS_E_ARG;
     const StageRule &rule = STAGE_RULES[stage];
     if (!rule.known || (rule.needs_iter && iter <= 0) || (P.fx_sums && !rule.fx_sums) ||
-        (P.roww && !rule.roww))
+        (P.roww && !rule.roww) || (P.reg_w && !rule.reg))
         return BSLS_E_ARG;
     switch (stage) {
         case BSLS_STAGE_RESET:  // reset scalars and tickets
@@ -228,12 +235,14 @@ extern "C" int bsls_bb_prologue(const bsls_bb_problem *p, void *stream) {
     int e;
     if ((e = bsls_bb_stage(p, BSLS_STAGE_RESET, 0, stream)) != BSLS_OK) return e;
     if ((e = bsls_bb_stage(p, BSLS_STAGE_Z_PLUS_ONE, 0, stream)) != BSLS_OK) return e;
+    if (P.reg_w) launch_bb_reg(P, P.z[1], 0, st);  // reg_g(z0 + 1) for g_prev
     launch_k1<true, false, false>(P, 0, w, st);  // r(z0 + 1)
     BSLS_LAUNCH_CHECK();
     if ((e = bsls_bb_stage(p, BSLS_STAGE_K2, 0, stream)) != BSLS_OK) return e;  // g_prev -> g[0]
     if ((e = bsls_bb_stage(p, BSLS_STAGE_Z2X, 0, stream)) != BSLS_OK) return e;
     // (fx_sums: max|r| of r(z0 + 1) was K2's; r(z0)'s alone is iteration 1's)
     BSLS_CHECK(clear_rmax(P, w, st));
+    if (P.reg_w) launch_bb_reg(P, P.z[0], 0, st);  // reg_g(z0), and f(z0)'s second term
     launch_k1<true, true, false>(P, 0, w, st);  // r(z0), f(z0)
     BSLS_LAUNCH_CHECK();
     return BSLS_OK;
@@ -251,9 +260,21 @@ extern "C" int bsls_bb_iterate(const bsls_bb_problem *p, int64_t first_iter, int
         const int zc = (int)((i - 1) & 1), zn = (int)(i & 1);
         launch_k2<true>(P, P.g[zc], P.g[zn], w, st);
         launch_k3(P, i, P.z[zc], P.g[zn], P.z[zn], w, st);
+        if (P.reg_w) launch_bb_reg(P, P.z[zn], i, st);
         launch_k1<true, true, true>(P, i, w, st);
         BSLS_LAUNCH_CHECK();
     }
+    return BSLS_OK;
+}
+
+extern "C" size_t bsls_bb_reg_work_size(int64_t n) { return reg_work_bytes(n > 0 ? n : 1); }
+
+extern "C" int bsls_bb_reg(const bsls_bb_problem *p, int zbuf, int64_t iter, void *stream) {
+    const int rc = check_problem(p);
+    if (rc != BSLS_OK) return rc;
+    if (!p->reg_w || zbuf < 0 || zbuf > 1) return BSLS_E_ARG;
+    launch_bb_reg(*p, p->z[zbuf], iter, (hipStream_t)stream);
+    BSLS_LAUNCH_CHECK();
     return BSLS_OK;
 }
 

@@ -88,11 +88,22 @@ __device__ __forceinline__ void bb_stop_check(const bsls_bb_problem &P, int64_t 
     if (reason) s[BSLS_S_STOP] = (double)reason;
 }
 
+// bsls_bb_problem.reg_work: the result word sum_i w_i xh_i^2 on a 64-B line of
+// its own, then bb_reg's tickets, then its partials (bb_reg.hpp)
+constexpr size_t REG_TICKET_OFF = 64;
+constexpr size_t REG_PART_OFF = REG_TICKET_OFF + ((TICKET_BYTES + 63) / 64) * 64;
+__device__ __forceinline__ double reg_sum_word(const bsls_bb_problem &P) {
+    return *reinterpret_cast<const double *>(P.reg_work);
+}
+
 __device__ __forceinline__ void bb_record_f(const bsls_bb_problem &P, int64_t iter, double rr,
                                             bool iterating) {
     double *s = P.scal;
     const double nr = sqrt(rr);
-    const double fx = 0.5 * (nr * nr);  // 0.5 * la.norm(r)**2, main.py:53
+    double fx = 0.5 * (nr * nr);  // 0.5 * la.norm(r)**2, main.py:53
+    // bsls_bb_problem.reg_w: + 0.5 sum_i w_i (N z + x0)_i^2, the word the
+    // bb_reg launched before this kernel left (CrossValidation.py:141)
+    if (P.reg_w) fx += 0.5 * reg_sum_word(P);
     s[BSLS_S_RR] = rr;
     s[BSLS_S_FX] = fx;
     if (iterating) {

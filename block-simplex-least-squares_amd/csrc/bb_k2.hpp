@@ -91,13 +91,18 @@ __device__ __forceinline__ void k2_store_sums(const bsls_bb_problem &P, int64_t 
 // walk the rows -- the halo row too -- are converted in place to doubles (one
 // group of a scaled incidence: to w_i = colv_i * sum, the epilogue's product),
 // and the group hand-off and the N' epilogue run as in the float form.
-template <int MODE, bool ITER, int FUSE = 0, int CV = 0, bool FX = false>
+// REG (bsls_bb_problem.reg_w: FUSE 0, !FX, gsel < 0): the epilogue loads
+// reg_g[j] with g_prev[j] and dz[j] and forms g = (w_i - w_{i+1}) + reg_g[j],
+// the reference's order (CrossValidation.py:142-144), before the store of g
+// and the four sums.
+template <int MODE, bool ITER, int FUSE = 0, int CV = 0, bool FX = false, bool REG = false>
 __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *__restrict__ dzv,
                                                const double *__restrict__ gp,
                                                double *__restrict__ gout, double *part,
                                                unsigned *ticket, unsigned *tk2rb, int64_t iter,
                                                int gsel, const unsigned long long *rmax = nullptr) {
     static_assert(!FX || (FUSE == 0 && (MODE == 1 || MODE == 3)), "FX: the single-GCD dealt K2");
+    static_assert(!REG || (FUSE == 0 && !FX), "REG: the single-GCD float K2");
     extern __shared__ __attribute__((aligned(16))) double lds[];
     __shared__ double red[5 * 16];
     __shared__ int row_last;
@@ -246,6 +251,7 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
         for (int64_t ib = threadIdx.x; ib < iend; ib += K2E * blockDim.x) {
             int32_t jq[K2E];
             double ca[K2E], cb[K2E], gq[K2E], dq[K2E];
+            [[maybe_unused]] double rq[REG ? K2E : 1];
 #pragma unroll
             for (int q = 0; q < K2E; ++q) {
                 const int64_t i = ib + (int64_t)q * blockDim.x;
@@ -264,6 +270,7 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
                     gq[q] = gp[jq[q]];
                     if (dzv) dq[q] = dzv[jq[q]];
                 }
+                if constexpr (REG) rq[q] = (jq[q] >= 0) ? P.reg_g[jq[q]] : 0.0;
             }
 #pragma unroll
             for (int q = 0; q < K2E; ++q) {
@@ -272,7 +279,8 @@ __global__ __launch_bounds__(1024) void bb_k2t(bsls_bb_problem P, const double *
                 if (j < 0) continue;
                 const double wa = scale_epi ? ca[q] * rows[i] : rows[i];
                 const double wb = scale_epi ? cb[q] * rows[i + 1] : rows[i + 1];
-                const double gv = wa - wb;
+                double gv = wa - wb;
+                if constexpr (REG) gv = gv + rq[q];
                 gout[j] = gv;
                 if (ITER) {
                     const double dg = gv - gq[q];
@@ -347,7 +355,8 @@ __global__ void bb_shard_record(bsls_bb_problem P, int64_t iter) {
 // no faster).  The ITER epilogue reads g_prev and dz = z - z_prev (K3 wrote
 // dz from the z's it holds, bit-identical to the subtraction here): 15.2 MB
 // that no walk overlaps, where z and z_prev were 22.8 MB.
-template <int MODE, bool ITER, int FUSE = 0>
+// REG: as bb_k2t.
+template <int MODE, bool ITER, int FUSE = 0, bool REG = false>
 __global__ __launch_bounds__(1024) void bb_k2(bsls_bb_problem P, const double *__restrict__ dzv,
                                               const double *__restrict__ gp,
                                               double *__restrict__ gout, double *part,
@@ -392,6 +401,8 @@ __global__ __launch_bounds__(1024) void bb_k2(bsls_bb_problem P, const double *_
     // epilogue operands: unconditional loads at clamped indices, all in flight
     int32_t j[4];
     double gpj[4], dzj[4];
+    [[maybe_unused]] double rgj[REG ? 4 : 1];
+    static_assert(!REG || FUSE == 0, "REG: the single-GCD K2");
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const int pos = 64 * q + lane;
@@ -408,10 +419,15 @@ __global__ __launch_bounds__(1024) void bb_k2(bsls_bb_problem P, const double *_
             dzj[q] = dzv ? dzv[jc] : 0.0;
         }
     }
+    if constexpr (REG) {
+#pragma unroll
+        for (int q = 0; q < 4; ++q) rgj[q] = P.reg_g[j[q] >= 0 ? j[q] : 0];
+    }
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         if (j[q] >= 0) {
-            const double g = s[q] - nx[q];
+            double g = s[q] - nx[q];
+            if constexpr (REG) g = g + rgj[q];
             gout[j[q]] = g;
             if (ITER) {
                 const double dg = g - gpj[q];

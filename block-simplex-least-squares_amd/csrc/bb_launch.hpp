@@ -240,24 +240,34 @@ static hipError_t clear_rmax(const bsls_bb_problem &P, const BBWork &w, hipStrea
 
 // (dz: the vector the ITER sums dot with delta_g -- the workspace's z - z_prev
 // unless given: the line search passes its direction d, with g_prev = 0)
-template <int MODE, bool ITER, int FUSE>
+// (REG: bsls_bb_problem.reg_w -- the launches that refuse it never get here
+// with it set: check_problem_float, bsls_bb_stage's table)
+template <int MODE, bool ITER, int FUSE, bool REG = false>
 static void launch_bb_k2(const bsls_bb_problem &P, const double *gp, double *gout,
                          const BBWork &w, hipStream_t st, int64_t iter, const double *dz) {
-    allow_lds(bb_k2<MODE, ITER, FUSE>);
-    bb_k2<MODE, ITER, FUSE><<<grid_for(P.AT.npanels, PANEL_WAVES), 1024, panel_lds_bytes(P.AT),
-                              st>>>(P, dz, gp, gout, w.p2, w.tk2, iter);
+    if constexpr (FUSE == 0 && !REG) {
+        if (P.reg_w) {
+            launch_bb_k2<MODE, ITER, 0, true>(P, gp, gout, w, st, iter, dz);
+            return;
+        }
+    }
+    allow_lds(bb_k2<MODE, ITER, FUSE, REG>);
+    bb_k2<MODE, ITER, FUSE, REG><<<grid_for(P.AT.npanels, PANEL_WAVES), 1024,
+                                   panel_lds_bytes(P.AT), st>>>(P, dz, gp, gout, w.p2, w.tk2,
+                                                                iter);
 }
 
 // (gsel >= 0: one column group, a workgroup per row block; two words per row in
 // LDS for FX's integer sums and MODE 2's scales beside the sums)
-template <int MODE, bool ITER, int FUSE, int CV, bool FX>
+template <int MODE, bool ITER, int FUSE, int CV, bool FX, bool REG = false>
 static void launch_bb_k2t(const bsls_bb_problem &P, const double *gp, double *gout,
                           const BBWork &w, hipStream_t st, int64_t iter, const double *dz,
                           int gsel) {
-    allow_lds(bb_k2t<MODE, ITER, FUSE, CV, FX>);
-    bb_k2t<MODE, ITER, FUSE, CV, FX><<<(int)(gsel >= 0 ? P.ATt.nrb : P.ATt.nrb * P.ATt.ngroups),
-                                       BSLS_TILE_THREADS,
-                                       tile_lds_doubles(P.ATt, FX || MODE == 2) * 8, st>>>(
+    allow_lds(bb_k2t<MODE, ITER, FUSE, CV, FX, REG>);
+    bb_k2t<MODE, ITER, FUSE, CV, FX, REG><<<(int)(gsel >= 0 ? P.ATt.nrb
+                                                            : P.ATt.nrb * P.ATt.ngroups),
+                                            BSLS_TILE_THREADS,
+                                            tile_lds_doubles(P.ATt, FX || MODE == 2) * 8, st>>>(
         P, dz, gp, gout, w.p2, w.tk2, w.tk2rb, iter, gsel, FX ? w.rmax : nullptr);
 }
 
@@ -269,6 +279,13 @@ static void launch_k2t_cv(const bsls_bb_problem &P, const double *gp, double *go
         // fx_sums (check_problem: a dealt image; bsls_bb_k2_part rejects it)
         if (P.fx_sums && gsel < 0) {
             launch_bb_k2t<MODE, ITER, 0, CV, true>(P, gp, gout, w, st, iter, dz, gsel);
+            return;
+        }
+    }
+    if constexpr (FUSE == 0) {
+        // reg_w (check_problem: never with fx_sums; bsls_bb_k2_part rejects it)
+        if (P.reg_w && gsel < 0) {
+            launch_bb_k2t<MODE, ITER, 0, CV, false, true>(P, gp, gout, w, st, iter, dz, gsel);
             return;
         }
     }
@@ -407,6 +424,11 @@ static int check_problem(const bsls_bb_problem *p) {
     // row weights: the whole problem on this GCD, float row sums, ordered group sums
     if (p->roww && (p->shard_role != 0 || p->r_fx != 0.0 || p->fx_sums != 0 || p->k1_atomic == 2))
         return BSLS_E_ARG;
+    // the regulariser: the whole problem on this GCD, float row sums, ordered
+    // group sums (composes with roww), and its two buffers
+    if (p->reg_w && (p->shard_role != 0 || p->r_fx != 0.0 || p->fx_sums != 0 ||
+                     p->k1_atomic == 2 || !p->reg_g || !p->reg_work))
+        return BSLS_E_ARG;
     if (p->At.ent) {
         if (!tiles_valid(p->At, p->m, p->n, 0, general, false, PANEL_LDS_MAX)) return BSLS_E_ARG;
         if (p->At.ngroups > 1 && !p->rpart) return BSLS_E_ARG;
@@ -431,11 +453,11 @@ static int check_problem(const bsls_bb_problem *p) {
     return BSLS_OK;
 }
 
-// the entry points that fx_sums and roww do not cover (include/bsls_hip.h)
+// the entry points that fx_sums, roww and reg_w do not cover (include/bsls_hip.h)
 static int check_problem_float(const bsls_bb_problem *p) {
     const int rc = check_problem(p);
     if (rc != BSLS_OK) return rc;
-    return (p->fx_sums || p->roww) ? BSLS_E_ARG : BSLS_OK;
+    return (p->fx_sums || p->roww || p->reg_w) ? BSLS_E_ARG : BSLS_OK;
 }
 
 }  // namespace bsls

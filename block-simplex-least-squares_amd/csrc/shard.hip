@@ -223,7 +223,7 @@ extern "C" int bsls_bb_shard_iterate(const bsls_bb_problem *p, bsls_comm *c, int
     if (!p || !c || first_iter < 1 || count < 0 || fuse < 0 || fuse > 2) return BSLS_E_ARG;
     if (p->shard_role != (c->rank == 0 ? 1 : 2)) return BSLS_E_ARG;   // target added once
     // fixed-point row sums, row weights: one GCD only
-    if (p->fx_sums || p->roww) return BSLS_E_ARG;
+    if (p->fx_sums || p->roww || p->reg_w) return BSLS_E_ARG;
     hipStream_t st = (hipStream_t)stream;
     // a sum over one rank is the identity: a one-rank communicator (the
     // rehearsal of one rank's share on one GPU) skips the collectives, whose
@@ -277,7 +277,9 @@ extern "C" int bsls_bb_shard_iterate_parts(const bsls_bb_problem *p, bsls_comm *
     if (!p || !c || !rb_bounds || first_iter < 1 || count < 0 || nparts < 2 ||
         nparts > MAX_PARTS || !comm_stream || comm_stream == stream)
         return BSLS_E_ARG;
-    if (p->shard_role != (c->rank == 0 ? 1 : 2) || p->fx_sums || p->roww) return BSLS_E_ARG;
+    if (p->shard_role != (c->rank == 0 ? 1 : 2) || p->fx_sums || p->roww ||
+        p->reg_w)
+        return BSLS_E_ARG;
     if (p->ATt.ngroups != nparts || !p->ATt.ent) return BSLS_E_ARG;
     int64_t R = 0;
     const int64_t nrb = bsls_bb_row_blocks(p, &R);

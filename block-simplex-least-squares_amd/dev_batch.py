@@ -6,7 +6,7 @@ import scipy.sparse as sps
 
 import _native
 from _native import check, stream_handle
-from dev_bb import poll_solve, row_weights_check
+from dev_bb import poll_solve, reg_lambda_check, row_weights_check
 from dev_blocks import BlockLayout, need_two_routes, particular_x0
 from dev_images import _torch
 
@@ -55,8 +55,11 @@ class BatchBB:
     repeats bit for bit."""
 
     def __init__(self, A, bs, block_sizes, row_weights=None, options=None, x0=None,
-                 early_exit=True):
+                 early_exit=True, reg_lambda=0.0, reg_weights=None):
         # everything that can be refused is refused here, before the device is touched
+        if reg_lambda_check(reg_lambda) or reg_weights is not None:
+            raise ValueError('the batched engine does not cover a regulariser: BBEngine, one '
+                             'problem at a time')
         A = sps.csr_matrix(A)
         self.m = int(A.shape[0])
         cols = _batch_columns(bs, self.m)

@@ -1,6 +1,7 @@
 """The fused z-space BB engine: its option checks, BBEngine (set up in named
 stages), the device line search that runs on it, and the BB host loop that
 BBEngine.solve and BatchBB.solve share."""
+import contextlib
 import ctypes
 import os
 import time
@@ -133,6 +134,86 @@ def row_weights_check(w, m):
     return w
 
 
+def reg_lambda_check(lam):
+    """The regulariser's lambda as a float: finite and >= 0 (None is 0);
+    anything else is a ValueError.  Pure host."""
+    if lam is None:
+        return 0.0
+    if isinstance(lam, bool) or not np.isscalar(lam) or isinstance(lam, (str, bytes)):
+        raise ValueError('reg_lambda must be a number (got %r)' % (lam,))
+    lam = float(lam)
+    if not np.isfinite(lam) or lam < 0:
+        raise ValueError('reg_lambda must be finite and >= 0 (got %r)' % (lam,))
+    return lam
+
+
+def reg_weights_check(d, n):
+    """The regulariser's per-route weights d as n finite, non-negative float64
+    values on the host (None stays None: ones); anything else is a ValueError.
+    Pure host."""
+    if d is None:
+        return None
+    if hasattr(d, 'detach'):
+        d = d.detach().cpu().numpy()
+    d = np.ascontiguousarray(np.asarray(d, dtype=np.float64).reshape(-1))
+    if d.size != int(n):
+        raise ValueError('reg_weights has %d entries, expected one per route (%d)'
+                         % (d.size, int(n)))
+    if not np.all(np.isfinite(d)):
+        raise ValueError('reg_weights must be finite (no NaN or inf)')
+    if np.any(d < 0):
+        raise ValueError('reg_weights must be non-negative')
+    return d
+
+
+def _wave_tree(v):
+    """block_sum's sums (bsls_common.hpp) over rows of 256 thread values: the
+    xor butterfly inside each wave of 64, then the waves left to right."""
+    v = np.asarray(v, dtype=np.float64).reshape(-1, 4, 64)
+    lane = np.arange(64)
+    for o in (32, 16, 8, 4, 2, 1):
+        v = v + v[:, :, lane ^ o]
+    w = v[:, :, 0]
+    return ((w[:, 0] + w[:, 1]) + w[:, 2]) + w[:, 3]
+
+
+def reg_model(z, layout, w):
+    """NumPy model of the bb_reg kernel (csrc/bb_reg.hpp): for the block layout
+    `layout` (a BlockLayout or the block sizes), z (nz) and w (n per-route
+    weights lambda d^2), returns (reg_g, total) -- reg_g = N'(w * (N z + x0)),
+    the roundings NumPy's NT.dot(w * (N.dot(z) + x0)) has, and total = sum_i
+    w_i (N z + x0)_i^2 added in the kernel's order (256 entries to a
+    workgroup, block_sum's tree, then last_block_sum over the workgroups)."""
+    sizes = np.asarray(getattr(layout, 'sizes', layout), dtype=np.int64)
+    need_two_routes(sizes)
+    n, p = int(sizes.sum()), int(sizes.size)
+    z = np.asarray(z, dtype=np.float64).reshape(-1)
+    w = np.asarray(w, dtype=np.float64).reshape(-1)
+    if z.size != n - p or w.size != n:
+        raise ValueError('reg_model: z has %d entries and w %d for n = %d, nz = %d'
+                         % (z.size, w.size, n, n - p))
+    xz = np.arange(n, dtype=np.int64) - np.repeat(np.arange(p, dtype=np.int64), sizes)
+    xz[np.cumsum(sizes) - 1] = -1
+    jp = np.concatenate(([-1], xz[:-1]))
+    zp = np.where(jp >= 0, z[np.maximum(jp, 0)], 0.0)
+    xh = np.where(xz >= 0, z[np.maximum(xz, 0)] - zp, (0.0 - zp) + 1.0)
+    q = w * xh
+    live = xz >= 0
+    reg_g = np.zeros(n - p)
+    reg_g[xz[live]] = (0.0 + q[live]) - q[np.nonzero(live)[0] + 1]
+    # the sum: per workgroup, then thread t of the last workgroup adds slots
+    # t, t + 256, .. in order before one more tree
+    nb = -(-n // 256)
+    t = np.zeros(nb * 256)
+    t[:n] = q * xh
+    part = _wave_tree(t)
+    acc = np.zeros(256)
+    for lo in range(0, nb, 256):
+        seg = part[lo:lo + 256]
+        acc[:seg.size] = acc[:seg.size] + seg
+    return reg_g, float(_wave_tree(acc)[0])
+
+
 def fixed_plan_fits(plan, halo):
     """Whether a tile plan (H, groups, order) leaves the LDS room for the two
     words per row of the fixed-point sums."""
@@ -220,7 +301,11 @@ class BBEngine:
     def __init__(self, A, b, block_sizes, options=None, early_exit=True, A_dev=None,
                  AT_dev=None, AT=None, target=None, x0=None, general=False, fmt=None,
                  tile_plans=(None, None), colv=None, deterministic=False, tile_layouts=None,
-                 link_parts=None, fixed_sums=None, row_weights=None):
+                 link_parts=None, fixed_sums=None, row_weights=None, reg_lambda=0.0,
+                 reg_weights=None):
+        # reg_lambda / reg_weights: the reference's weighted L2 regulariser,
+        # + 0.5 lambda ||d o (N z + x0)||^2 (bsls_bb_problem.reg_w;
+        # set_regulariser changes lambda or d between solves on the same images).
         # fixed_sums: order-free fixed-point row sums on the dealt tiles
         # (bsls_bb_problem.fx_sums) -- bit-reproducible iterates and exit
         # iterations from the default engine's walks.  row_weights: per-link
@@ -228,7 +313,8 @@ class BBEngine:
         # held-out fold -- set_row_weights swaps them between solves on the
         # same images.  The stages, in the order the device sees them:
         o = self._resolve(A, AT, block_sizes, general, fmt, colv, deterministic, tile_layouts,
-                          link_parts, fixed_sums, row_weights, target)
+                          link_parts, fixed_sums, row_weights, target, reg_lambda, reg_weights,
+                          x0)
         _native.lib()                      # (a missing library fails before any upload)
         self.layout = BlockLayout(o.sizes)
         self._A_dev, self._AT_dev = A_dev, AT_dev
@@ -237,9 +323,14 @@ class BBEngine:
         xin = self._allocate(o, b, x0, target)
         self._fill_problem(o, early_exit)
         self._form_target(xin, o.row_weights)
+        if o.reg_lambda > 0.0:
+            self.set_regulariser(o.reg_lambda, o.reg_weights)
+        elif o.reg_weights is not None:
+            self.set_regulariser(0.0, o.reg_weights)      # (d kept for a later lambda)
 
     def _resolve(self, A, AT, block_sizes, general, fmt, colv, deterministic, tile_layouts,
-                 link_parts, fixed_sums, row_weights, target):
+                 link_parts, fixed_sums, row_weights, target, reg_lambda=0.0, reg_weights=None,
+                 x0=None):
         """Stage 1, host only (no library call, no torch): every option and
         environment switch resolved once, and everything that can be refused
         on them refused.  Sets the engine's option attributes and returns the
@@ -286,6 +377,17 @@ class BBEngine:
             raise ValueError('A has %d columns but the blocks cover %d'
                              % (A.shape[1], int(sizes.sum())))
         need_two_routes(sizes)
+        # the regulariser: the device forms N z + x0 with the particular x0
+        # (1 at each block's last entry), so an engine built on another x0, or
+        # on a column shard's target, cannot carry it
+        self.reg_lambda, self.reg_d, self.reg_w = 0.0, None, None
+        self._reg_ok = target is None and (
+            x0 is None or np.array_equal(np.asarray(x0, dtype=np.float64).reshape(-1),
+                                         particular_x0(sizes)))
+        reg_lambda = reg_lambda_check(reg_lambda)
+        reg_weights = reg_weights_check(reg_weights, A.shape[1])
+        if reg_lambda > 0.0:
+            self._reg_refusals(k1_atomic)
         AT = sps.csr_matrix(AT) if AT is not None else A.T.tocsr()
         # values dropped for a scaled incidence (colv: the caller's column
         # scales, else detected)
@@ -299,6 +401,7 @@ class BBEngine:
         self.fmt_AT = spmv_format(AT, fmt, dealt=tile_layouts[1] in (1, 2))
         return SimpleNamespace(
             A=A, AT=AT, sizes=sizes, colv=colv, row_weights=row_weights, parts=parts,
+            reg_lambda=reg_lambda, reg_weights=reg_weights,
             pava_warm=warm if warm is not None else (0 if deterministic else 1),
             k1_atomic=k1_atomic, k3_merge=k3_merge)
 
@@ -542,6 +645,73 @@ class BBEngine:
         self.row_weights = torch.from_numpy(w).cuda()
         self.P.roww = self.row_weights.data_ptr()
 
+    def _reg_refusals(self, k1_atomic, shard_role=0, r_fx=0.0):
+        """What a regulariser cannot be combined with (ValueError); host only."""
+        if self.fixed_sums:
+            raise ValueError('a regulariser is not covered by fixed_sums: build the engine '
+                             'without one of them')
+        if not self._reg_ok:
+            raise ValueError('a regulariser needs the whole problem on the particular x0 '
+                             '(1 at each block\'s last entry): not a column shard\'s target '
+                             'or another x0')
+        if shard_role != 0 or r_fx > 0:
+            raise ValueError('a regulariser is not covered on a column shard')
+        if k1_atomic == 2:
+            raise ValueError('a regulariser keeps the ordered group sums: BSLS_K1_ATOMIC=1 '
+                             'does not go with it')
+
+    def set_regulariser(self, lam, d=None):
+        """The weighted L2 regulariser for what runs next (the reference's
+        reg = 'L2', python/CrossValidation.py:140-148): f gains 0.5 lam ||d o
+        (N z + x0)||^2 and nabla_f gains N'(lam d^2 o (N z + x0)).  d: n finite
+        values >= 0 (kept on the device; None keeps the last d, ones at
+        first -- the reference's plain reg = 'L2'); lam finite and >= 0, 0 or
+        None for no regulariser.  The engine forms reg_w = lam * d * d on the
+        device; the images, the workspace and target stay, so one engine
+        serves every lambda of a path."""
+        lam = reg_lambda_check(lam)
+        d = reg_weights_check(d, self.n)
+        torch = _torch()
+        if d is not None:
+            self.reg_d = torch.from_numpy(d).cuda()
+        if lam == 0.0:
+            self.reg_lambda = 0.0
+            self.P.reg_w = None
+            return
+        self._reg_refusals(self.P.k1_atomic, self.P.shard_role, self.P.r_fx)
+        dev = dict(dtype=torch.float64, device='cuda')
+        if self.reg_d is None:
+            self.reg_d = torch.ones(self.n, **dev)
+        if self.reg_w is None:
+            self.reg_w = torch.empty(self.n, **dev)
+            self.reg_g = torch.zeros(max(self.nz, 1), **dev)
+            self.reg_work = torch.zeros(_native.lib().bsls_bb_reg_work_size(self.n),
+                                        dtype=torch.uint8, device='cuda')
+        torch.mul(self.reg_d * lam, self.reg_d, out=self.reg_w)     # (lam * d) * d
+        self.reg_lambda = lam
+        self.P.reg_w, self.P.reg_g, self.P.reg_work = (
+            self.reg_w.data_ptr(), self.reg_g.data_ptr(), self.reg_work.data_ptr())
+
+    def _unregularised_only(self, what):
+        if self.reg_lambda:
+            raise ValueError('%s is not covered by a regulariser (BB only): '
+                             'set_regulariser(0) first' % what)
+
+    def _reg_terms(self):
+        """bsls_bb_reg at z[0], outside an iteration: between Z2X and K1."""
+        if self.reg_lambda:
+            check(_native.lib().bsls_bb_reg(self.P, 0, 0, stream_handle()), 'bsls_bb_reg')
+
+    @contextlib.contextmanager
+    def _plain(self):
+        """The regulariser's pointer cleared for a call of the plain operators."""
+        keep = self.P.reg_w
+        self.P.reg_w = None
+        try:
+            yield
+        finally:
+            self.P.reg_w = keep
+
     def held_out(self):
         """0.5 sum of r_i^2 over the rows with weight 0 (r the plain residual)
         at the last solve() / f(z); 0.0 on an unweighted engine."""
@@ -605,6 +775,8 @@ class BBEngine:
         if scale > 0:
             self._fixed_only_bb('a fixed-point r')
         self._unweighted_only('a fixed-point r')
+        if scale > 0:
+            self._unregularised_only('a fixed-point r')
         if scale < 0 or (scale > 0 and not self.fixed_r_ok()):
             raise ValueError('fixed-point r needs an atomic sharded K1 (fixed_r_ok)')
         self.P.r_fx = scale
@@ -631,6 +803,7 @@ class BBEngine:
         if role != 0:
             self._fixed_only_bb('a column shard')
             self._unweighted_only('a column shard')
+            self._unregularised_only('a column shard')
         self.P.shard_role = int(role)
 
     def row_blocks(self):
@@ -698,14 +871,16 @@ class BBEngine:
         Unweighted, as apply_A_x and apply_AT: row_weights act on residual, f
         and nabla_f only."""
         self._fixed_only_bb('apply_A (DORE)')
-        self._x_of(z)
-        self.stage(_native.STAGE_K1_PARTIAL, 0)
+        with self._plain():
+            self._x_of(z)
+            self.stage(_native.STAGE_K1_PARTIAL, 0)
         return self.r * alpha if alpha != 1.0 else self.r.clone()
 
     def apply_AT(self, r, alpha=1.0):
         """alpha N' A' r (DORE's linop_T)."""
         self.load_r(r)
-        self.stage(_native.STAGE_K2, 0)
+        with self._plain():
+            self.stage(_native.STAGE_K2, 0)
         g = self.g[0][:self.nz]
         return g * alpha if alpha != 1.0 else g.clone()
 
@@ -713,20 +888,24 @@ class BBEngine:
         """alpha (A N z + target) (DORE scales A and target by alpha); with
         row_weights w the weighted residual, alpha w * (A N z + target)."""
         self._x_of(z)
+        self._reg_terms()
         self.stage(_native.STAGE_K1, 0)
         return self.r * alpha if alpha != 1.0 else self.r.clone()
 
     def f(self, z):
         """0.5 ||A N z + target||^2 (main.py:53), f as K1's finish forms it; with
-        row_weights w, 0.5 sum w_i r_i^2 (and held_out() the zero-weight rows')."""
+        row_weights w, 0.5 sum w_i r_i^2 (and held_out() the zero-weight rows');
+        with a regulariser + 0.5 lam ||d o (N z + x0)||^2."""
         self._x_of(z)
+        self._reg_terms()
         self.stage(_native.STAGE_K1, 0)
         return float(self.scal[_native.S_FX].item())
 
     def nabla_f(self, z):
         """N' A' (A N z + target) (main.py:54); with row_weights w,
-        N' A' (w * (A N z + target))."""
+        N' A' (w * (A N z + target)); with a regulariser + N'(lam d^2 o (N z + x0))."""
         self._x_of(z)
+        self._reg_terms()
         self.stage(_native.STAGE_K1, 0)
         self.stage(_native.STAGE_K2, 0)
         return self.g[0][:self.nz].clone()
@@ -735,6 +914,7 @@ class BBEngine:
         """This engine's device weak Wolfe line search (LBFGS.solve)."""
         self._fixed_only_bb('the line search')
         self._unweighted_only('the line search')
+        self._unregularised_only('the line search')
         ls = getattr(self, '_ls', None)
         if ls is None:
             ls = self._ls = LineSearch(self)
@@ -748,7 +928,8 @@ class BBEngine:
             # (the stage without target is not covered: the general CSR kernel)
             return self.A.matvec(x)
         self.x.copy_(self.colv * x if self.scaled else x)
-        self.stage(_native.STAGE_K1_PARTIAL, 0)
+        with self._plain():
+            self.stage(_native.STAGE_K1_PARTIAL, 0)
         return self.r.clone()
 
     def proj(self, z):

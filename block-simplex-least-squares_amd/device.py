@@ -26,5 +26,5 @@ from dev_images import (NT_BYTES, DeviceCSR, DevicePanels, DeviceTiles, PanelOve
 from dev_blocks import BlockLayout, IsoPlan, _cur_dev, _iso_plans, iso_mode, iso_plan
 from dev_lsq import DeviceLSQ, XBBEngine, lsq_operator
 from dev_bb import (BBEngine, LineSearch, fixed_plan_fits, fixed_sum_bounds, fixed_sums_check,
-                    row_weights_check)
+                    reg_lambda_check, reg_model, reg_weights_check, row_weights_check)
 from dev_batch import BatchBB, _batch_columns, batch_groups, batch_width

@@ -112,6 +112,9 @@ class ShardedBB:
         if getattr(engine, 'row_weights', None) is not None:
             raise ValueError('a column shard is not covered by row_weights: '
                              'set_row_weights(None) first')
+        if getattr(engine, 'reg_lambda', 0.0):
+            raise ValueError('a column shard is not covered by a regulariser: '
+                             'set_regulariser(0) first')
         self.e = engine
         rank = _shard_rank(rank)
         # link parts: an engine built with link_parts = parts (K2's image in

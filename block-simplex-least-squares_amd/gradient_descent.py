@@ -66,6 +66,9 @@ class GradientDescent:
         if e is not None and getattr(e, 'row_weights', None) is not None and self.method != 'BB':
             raise ValueError('method %r does not run on an engine with row_weights: '
                              'BB only' % self.method)
+        if e is not None and getattr(e, 'reg_lambda', 0.0) and self.method != 'BB':
+            raise ValueError('method %r does not run on an engine with a regulariser: '
+                             'BB only' % self.method)
         if self.method == 'LBFGS':
             f, nabla_f, proj = self._device_closures() if e else (self.f, self.nabla_f, self.proj)
             z0 = self._z0_device() if e else self.z0

@@ -50,6 +50,10 @@ def parser():
     p.add_argument('--cv-batch', dest='cv_batch', type=int, default=None, metavar='R',
                    help='with --cv: run the folds R (1..8) at a time in lockstep on one batched '
                         'engine (device.BatchBB) instead of one after another')
+    p.add_argument('--reg', dest='reg', type=float, default=None, metavar='LAMBDA',
+                   help='the reference\'s L2 regulariser, + 0.5 LAMBDA ||N z + x0||^2 '
+                        '(CrossValidation.py:145-148, ISTTT.py:88-92; method BB only; per-route '
+                        'weights through the API: build_engine(reg_weights=))')
     return p
 
 
@@ -61,7 +65,7 @@ def deterministic_default():
 
 
 def build_engine(A, b, x0, block_sizes, options=None, deterministic=None, reproducible=None,
-                 row_weights=None):
+                 row_weights=None, reg_lambda=0.0, reg_weights=None):
     """The device engine of solve_in_z's closures.  deterministic=True keeps
     every SpMV row sum in a fixed order (panels / thread-stream tiles): runs are
     bit-reproducible, so the exact-zero exit of BB.py:22 and the exit iteration
@@ -70,22 +74,26 @@ def build_engine(A, b, x0, block_sizes, options=None, deterministic=None, reprod
     sums their rows in fixed point instead (order-free: bit-reproducible too;
     BB only); None leaves it to BSLS_FIXED_SUMS (BBEngine(fixed_sums=None)).
     row_weights: per-link weights w, f = 0.5 sum w_i r_i^2 (BB only; not with
-    reproducible)."""
-    from device import BBEngine
+    reproducible).  reg_lambda / reg_weights: the weighted L2 regulariser, f +
+    0.5 lambda ||d o (N z + x0)||^2 (BB only; not with reproducible; x0 the
+    particular solution)."""
+    from device import BBEngine, reg_lambda_check
     if deterministic is None:
         deterministic = deterministic_default() and not reproducible
+    plain = (row_weights is None and not reg_lambda_check(reg_lambda)
+             and reg_weights is None)
     return BBEngine(A, b, block_sizes, options=options, x0=x0, deterministic=bool(deterministic),
-                    fixed_sums=(True if reproducible else
-                                (False if row_weights is not None else None)),
-                    row_weights=row_weights)
+                    fixed_sums=(True if reproducible else (None if plain else False)),
+                    row_weights=row_weights, reg_lambda=reg_lambda, reg_weights=reg_weights)
 
 
 def solve_in_z(A, b, x0, N, block_sizes, method, options=None, engine=None, deterministic=None,
-               row_weights=None):
+               row_weights=None, reg_lambda=0.0, reg_weights=None):
     """python/main.py:41-79 on the device.  N is accepted for signature
     compatibility and never used: the engine applies N / N' as per-block
-    differences without materialising it.  row_weights (BB only) go to the
-    engine built here; an engine passed in keeps its own."""
+    differences without materialising it.  row_weights and reg_lambda /
+    reg_weights (BB only) go to the engine built here; an engine passed in
+    keeps its own."""
     if block_sizes is not None and len(block_sizes) == A.shape[1]:
         logging.error('Trivial example: nblocks == nroutes, exiting solver')
         sys.exit()
@@ -95,7 +103,8 @@ def solve_in_z(A, b, x0, N, block_sizes, method, options=None, engine=None, dete
     assert np.all(block_sizes >= 2)
     z0 = x2z(x0, block_sizes)
     eng = engine or build_engine(A, b, x0, block_sizes, deterministic=deterministic,
-                                 row_weights=row_weights)
+                                 row_weights=row_weights, reg_lambda=reg_lambda,
+                                 reg_weights=reg_weights)
     gd = GradientDescent(z0=z0, method=method, options=options, engine=eng)
     iters, times, states = gd.run()
     import torch
@@ -141,15 +150,52 @@ def solve_many(A, bs, x0, N, block_sizes, options=None, row_weights=None, batch=
     return out
 
 
-def solve_in_z_cpu(A, b, x0, N, block_sizes, method, options=None, row_weights=None):
+def host_closures(A, N, target, x0, row_weights=None, reg_lambda=0.0, reg_weights=None):
+    """(f, nabla_f) of the host path over SciPy: main.py:53-54; with
+    row_weights w the engine's weighted objective; with reg_lambda the
+    reference's regularised one as written at CrossValidation.py:141-144, D =
+    sqrt(lambda) d and D2 = lambda d^2 (d None: ones)."""
+    import numpy.linalg as la
+    from device import reg_lambda_check, reg_weights_check, row_weights_check
+    AT = A.T.tocsr()
+    NT = N.T.tocsr()
+    w = row_weights_check(row_weights, A.shape[0])
+    lam = reg_lambda_check(reg_lambda)
+    if w is not None:
+        def f0(z):
+            r = A.dot(N.dot(z)) + target
+            return 0.5 * np.sum(w * r * r)
+
+        def g0(z):
+            r = A.dot(N.dot(z)) + target
+            return NT.dot(AT.dot(w * r))
+    else:
+        f0 = lambda z: 0.5 * la.norm(A.dot(N.dot(z)) + target) ** 2
+        g0 = lambda z: NT.dot(AT.dot(A.dot(N.dot(z)) + target))
+    if not lam:
+        return f0, g0
+    d = reg_weights_check(reg_weights, A.shape[1])
+    if d is None:
+        d = np.ones(A.shape[1])
+    D, D2 = np.sqrt(lam) * d, lam * d * d
+    x0 = np.asarray(x0, dtype=np.float64)
+    f = lambda z: f0(z) + 0.5 * la.norm(D * (N.dot(z) + x0)) ** 2
+    nabla_f = lambda z: g0(z) + NT.dot(D2 * (N.dot(z) + x0))
+    return f, nabla_f
+
+
+def solve_in_z_cpu(A, b, x0, N, block_sizes, method, options=None, row_weights=None,
+                   reg_lambda=0.0, reg_weights=None):
     """python/main.py:41-79 on the host (BASELINE configs[0]): the reference's
     closures over SciPy csr_matvec, proj = the host c_extensions library's
     isotonic_regression_multi (include/bsls_cpu.h) + clip, the solver loops of
     BB.py / LBFGS.py / DORE.py over them.  row_weights w (BB only): the
-    engine's weighted objective, f = 0.5 sum w r^2, nabla_f = N'A'(w r)."""
-    import numpy.linalg as la
+    engine's weighted objective, f = 0.5 sum w r^2, nabla_f = N'A'(w r).
+    reg_lambda / reg_weights (BB only): the reference's regularised closures
+    (host_closures)."""
     from bsls_utils import particular_x0
     from c_extensions import _cpu
+    from device import reg_lambda_check
     if block_sizes is not None and len(block_sizes) == A.shape[1]:
         logging.error('Trivial example: nblocks == nroutes, exiting solver')
         sys.exit()
@@ -157,24 +203,11 @@ def solve_in_z_cpu(A, b, x0, N, block_sizes, method, options=None, row_weights=N
     assert np.all(block_sizes >= 2)
     z0 = x2z(x0, block_sizes)
     target = A.dot(x0) - b
-    AT = A.T.tocsr()
-    NT = N.T.tocsr()
-    if row_weights is not None:
-        from device import row_weights_check
-        if method != 'BB':
-            raise ValueError('row_weights cover method BB only (got %r)' % method)
-        w = row_weights_check(row_weights, A.shape[0])
-
-        def f(z):
-            r = A.dot(N.dot(z)) + target
-            return 0.5 * np.sum(w * r * r)
-
-        def nabla_f(z):
-            r = A.dot(N.dot(z)) + target
-            return NT.dot(AT.dot(w * r))
-    else:
-        f = lambda z: 0.5 * la.norm(A.dot(N.dot(z)) + target) ** 2
-        nabla_f = lambda z: NT.dot(AT.dot(A.dot(N.dot(z)) + target))
+    if row_weights is not None and method != 'BB':
+        raise ValueError('row_weights cover method BB only (got %r)' % method)
+    if reg_lambda_check(reg_lambda) and method != 'BB':
+        raise ValueError('a regulariser covers method BB only (got %r)' % method)
+    f, nabla_f = host_closures(A, N, target, x0, row_weights, reg_lambda, reg_weights)
     cum_blocks = np.concatenate(([0], np.cumsum(block_sizes - 1)))
 
     def proj(x):
@@ -307,7 +340,14 @@ def main(args=None, plot=False):
         raise ValueError('--cv covers --method BB only (got %r)' % args.method)
     if cv is not None and reproducible:
         raise ValueError('--cv and --reproducible exclude each other')
+    reg = getattr(args, 'reg', None)
+    if reg is not None and args.method != 'BB':
+        raise ValueError('--reg covers --method BB only (got %r)' % args.method)
+    if reg is not None and reproducible:
+        raise ValueError('--reg and --reproducible exclude each other')
     cv_batch = getattr(args, 'cv_batch', None)
+    if cv_batch is not None and cv is not None and reg:
+        raise ValueError('--cv-batch does not cover --reg')
     if cv_batch is not None and cv is None:
         raise ValueError('--cv-batch needs --cv')
     if cv_batch is not None and not 1 <= cv_batch <= 8:
@@ -321,6 +361,12 @@ def main(args=None, plot=False):
     bm.degree_reduced_form()
     AA, bb, N, block_sizes, x_split, nz, scaling, rsort_index, x0 = bm.get_LS()
     output = bm.info
+    if reg and not np.array_equal(np.asarray(x0, dtype=np.float64).reshape(-1),
+                                  particular_x0(block_sizes)):
+        # the device adds the particular x0 to N z itself; the host path would
+        # take any x0, so the same command is refused on both
+        raise ValueError('--reg needs the particular x0 (1 at each block\'s last route) as the '
+                         'initial solution: not with --init data that gives another')
     if args.noise:
         delta = np.random.normal(scale=bb * args.noise)
         bb = bb + delta
@@ -329,23 +375,26 @@ def main(args=None, plot=False):
         import _native
         device = 'cpu' if _native.device_mode() == 'cpu' else 'gpu'
     if device == 'cpu':
-        iters, times, states = solve_in_z_cpu(AA, bb, x0, N, block_sizes, args.method)
+        iters, times, states = solve_in_z_cpu(AA, bb, x0, N, block_sizes, args.method,
+                                              reg_lambda=reg or 0.0)
         x_last, error, output = LS_postprocess_cpu(states, x0, AA, bb, x_split, scaling=scaling,
                                                    block_sizes=block_sizes, N=N, output=output)
         if cv is not None:
             from cross_validation import kfold
-            output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, device='cpu', batch=cv_batch)
+            output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, device='cpu', batch=cv_batch,
+                                 reg_lambda=reg or 0.0)
         return iters, times, states, output
     eng = build_engine(AA, bb, x0, block_sizes,
                        deterministic=getattr(args, 'deterministic', None),
-                       reproducible=reproducible)
+                       reproducible=reproducible, reg_lambda=reg or 0.0)
     iters, times, states = solve_in_z(AA, bb, x0, N, block_sizes, args.method, engine=eng)
     x_last, error, output = LS_postprocess(states, x0, AA, bb, x_split, scaling=scaling,
                                            block_sizes=block_sizes, N=N, output=output,
                                            engine=eng)
     if cv is not None:
         from cross_validation import kfold
-        output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, engine=eng, batch=cv_batch)
+        output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, engine=eng, batch=cv_batch,
+                             reg_lambda=reg or 0.0)
     if plot:
         import matplotlib.pyplot as plt
         plt.figure(); plt.hist(x_last)

@@ -181,7 +181,8 @@ enum {
     BSLS_S_ITER = 1,       /* last completed iteration i */
     BSLS_S_ZBUF = 2,       /* index (0/1) of the z buffer holding the current iterate */
     BSLS_S_T = 3,          /* last BB step t */
-    BSLS_S_FX = 4,         /* f(z) = 0.5 ||r||^2 at the current iterate */
+    BSLS_S_FX = 4,         /* f(z) = 0.5 ||r||^2 at the current iterate; with
+                              bsls_bb_problem.reg_w + 0.5 sum_i w_i (N z + x0)_i^2 */
     BSLS_S_SUMDG = 5,      /* sum(delta_g) */
     BSLS_S_DZDG = 6,       /* delta_z . delta_g */
     BSLS_S_DGDG = 7,       /* delta_g . delta_g */
@@ -471,9 +472,49 @@ typedef struct bsls_bb_problem {
      * bsls_bb_shard_iterate, bsls_bb_shard_iterate_parts, and bsls_bb_stage 2,
      * 8, 9 and 10-15. */
     const double *roww;
+    /* n per-route weights w_i = lambda d_i^2 >= 0 (finite) of the weighted L2
+     * regulariser, or NULL: everything as without it.  Set, the objective is
+     * the reference's regularised one (python/CrossValidation.py:140-148;
+     * python/ISTTT.py:88-92 is d = 1),
+     *   f(z) = 0.5 ||A N z + target||^2 + 0.5 sum_i w_i xh_i^2,  xh = N z + x0,
+     *   grad f(z) = N'A'(A N z + target) + N'(w o xh),
+     * with x0 the particular solution (1 at each block's last entry).
+     * bsls_bb_reg forms reg_g = N'(w o xh) and sum_i w_i xh_i^2 for one z
+     * buffer; K2 adds reg_g[j] to (A'r)_i - (A'r)_{i+1} before it stores g and
+     * forms the BB sums, and every K1 finish that records f adds half the sum
+     * to scal[FX] (scal[RR] and scal[HELD] keep their meaning).  lambda is
+     * folded into the array, so changing it is one elementwise op and no
+     * image, workspace or target changes.  Composes with roww.  Needs
+     * shard_role 0, r_fx 0, fx_sums 0 and k1_atomic != 2, reg_g and reg_work;
+     * anything else is BSLS_E_ARG.
+     * Entry points that reject a regularised problem (BSLS_E_ARG):
+     * bsls_dore_iterate, bsls_lbfgs_ls_begin / _trials / _finish,
+     * bsls_bb_k2_part, bsls_bb_k1_rows, bsls_bb_residual_rows,
+     * bsls_bb_shard_iterate, bsls_bb_shard_iterate_parts, and bsls_bb_stage 2
+     * and 8-15. */
+    const double *reg_w;
+    /* reg_w: nz doubles, N'(w o xh) at the iterate the next K2 differentiates
+     * at (written by bsls_bb_reg). */
+    double *reg_g;
+    /* reg_w: bsls_bb_reg_work_size(n) bytes, zeroed once by the caller: the
+     * result word sum_i w_i xh_i^2 (the first double), the reduction's
+     * tickets and its per-workgroup partials. */
+    void *reg_work;
 } bsls_bb_problem;
 
 size_t bsls_bb_workspace_size(int64_t m, int64_t n, int64_t nz);
+/* Bytes of bsls_bb_problem.reg_work for n routes. */
+size_t bsls_bb_reg_work_size(int64_t n);
+/* The regulariser's terms at z[zbuf] (0 / 1) of a problem with reg_w: per x
+ * entry i, j = xz[i], jp = xz[i - 1] (-1 at i = 0), xh_i = z[j] - (jp >= 0 ?
+ * z[jp] : 0) or, at a block's last entry, (0 - z[jp]) + 1 -- N z + x0 as
+ * python/CrossValidation.py:141-144 forms it -- then q_i = w_i xh_i,
+ * reg_g[j] = q_i - q_{i+1} (the row of N') and sum_i q_i xh_i into reg_work's
+ * first double, reduced in a fixed order (two runs give the same bits).
+ * iter > 0 on a stopped run (scal[STOP] != 0) writes nothing.  bsls_bb_iterate
+ * and bsls_bb_prologue call it themselves; a caller of bsls_bb_stage runs it
+ * between stages 6 and 7.  BSLS_E_ARG without reg_w or with zbuf outside 0, 1. */
+int bsls_bb_reg(const bsls_bb_problem *p, int zbuf, int64_t iter, void *stream);
 /* Byte offset in `work` of dz = z - z_prev (nz doubles), the hand-off K3 writes
  * for the next K2 (and the prologue for iteration 1); for tests and tools. */
 size_t bsls_bb_dz_offset(int64_t m, int64_t n, int64_t nz);
@@ -542,7 +583,8 @@ enum bsls_stage {
     BSLS_STAGE_K3_RECORD_INIT = 15
 };
 /* One iteration i >= 1 = 3, [allreduce sums], 4, 1, [allreduce r], 2; on one GCD
- * bsls_bb_iterate runs 3, 4, 7.  The column-sharded driver (distributed.py,
+ * bsls_bb_iterate runs 3, 4, 7 (with reg_w: 3, 4, bsls_bb_reg on z[i & 1], 7;
+ * python/CrossValidation.py:141-144).  The column-sharded driver (distributed.py,
  * shard_role 1 / 2) runs 8, [allreduce sums], 4, 1, [allreduce r] per
  * iteration and 9 after the last one (fuse 1), or the sliced form 10,
  * [allreduce 5 sums], 15, 14, [allreduce r] (fuse 2, the default; both the
