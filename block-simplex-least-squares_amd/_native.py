@@ -236,6 +236,9 @@ _SIGS = {
     'bsls_bbm_prologue': (_int, [ctypes.POINTER(BBMProblem), _vp]),
     'bsls_bbm_iterate': (_int, [ctypes.POINTER(BBMProblem), _i64, _i64, _vp]),
     'bsls_bbm_stage': (_int, [ctypes.POINTER(BBMProblem), _int, _i64, _vp]),
+    'bsls_link_metrics_work_size': (_sz, [_i64, _int, _int]),
+    'bsls_link_metrics': (_int, [_vp, _i64, _vp, _vp, _i64, _vp, _int, _i64, _int, _vp, _vp,
+                                 _vp]),
     'bsls_lbfgs_ls_work_size': (_sz, [_i64]),
     'bsls_lbfgs_ls_begin': (_int, [ctypes.POINTER(BBProblem), ctypes.POINTER(LsState), _vp]),
     'bsls_lbfgs_ls_trials': (_int, [ctypes.POINTER(BBProblem), ctypes.POINTER(LsState), _i64,
@@ -364,8 +367,10 @@ def load():
         L = ctypes.CDLL(LIB_PATH)
         for name, (res, args) in _SIGS.items():
             # (BSLS_LIB: the parent build timed against this one, tools/reg_ab.py,
-            # lacks the regulariser's two entry points; calling one still raises)
-            if (name in ('bsls_bb_reg', 'bsls_bb_reg_work_size') and os.environ.get('BSLS_LIB')
+            # lacks the regulariser's two entry points and the link metrics' two;
+            # calling one still raises)
+            if (name in ('bsls_bb_reg', 'bsls_bb_reg_work_size', 'bsls_link_metrics',
+                         'bsls_link_metrics_work_size') and os.environ.get('BSLS_LIB')
                     and not hasattr(L, name)):
                 continue
             fn = getattr(L, name)

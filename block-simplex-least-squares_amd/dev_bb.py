@@ -484,6 +484,7 @@ class BBEngine:
         lay, colv = self.layout, o.colv
         dev = dict(dtype=torch.float64, device='cuda')
         self.x0 = x0 = particular_x0(lay.sizes, on_device=True)
+        self.b = self._b_host = self._x0_own = None
         if target is not None:
             # column-sharded: the caller formed sum_g A_g x0_g - b (distributed.py)
             self.target = torch.as_tensor(target, dtype=torch.float64).cuda().contiguous()
@@ -494,6 +495,11 @@ class BBEngine:
             # as BSLSMatrices.initial_solution does
             xin = x0 if x is None else torch.as_tensor(np.asarray(x, dtype=np.float64)).cuda()
             self.target = -torch.as_tensor(np.asarray(b, dtype=np.float64)).cuda()
+            self._x0_own = None if x is None else xin.reshape(-1)
+        # b stays on the device for link_metrics (target is A x0 - b by stage 5)
+        if b is not None:
+            self._b_host = np.ascontiguousarray(np.asarray(b, dtype=np.float64).reshape(-1))
+            self.b = torch.from_numpy(self._b_host).cuda()
         self.z = [torch.zeros(max(self.nz, 1), **dev) for _ in range(2)]
         self.g = [torch.zeros(max(self.nz, 1), **dev) for _ in range(2)]
         self.x = torch.empty(lay.n, **dev)
@@ -718,6 +724,51 @@ class BBEngine:
         if self.row_weights is None:
             return 0.0
         return 0.5 * float(self.scal[_native.S_HELD].item())
+
+    def link_metrics(self, z=None, nbins=6, edges=None):
+        """The reference's link metrics of the fit (dev_metrics.metrics_from_cells:
+        GEH, RMSE, pRMSE and error over the train and the held-out links, and
+        per link class by flow) at z: None (the z of the last solve()), one z,
+        or a list of z (logged states, device or host; the figures are then
+        arrays over them).  x_hat = x0 + N z, A x_hat by apply_A_x (unweighted;
+        the general CSR under fixed_sums), then one bsls_link_metrics launch
+        over every state with row_weights as the mask (none: every link is
+        train).  edges: the class edges, else link_classes(b, nbins).  The
+        metrics are of the plain residual, with a regulariser too.  Overwrites
+        the x / r scratch as apply_A_x does; scal, z, g, the weights and the
+        regulariser stay."""
+        import dev_metrics
+        if self.b is None:
+            raise ValueError('link metrics need b: this engine was built from a target '
+                             'without one')
+        if self.P.shard_role != 0 or self.P.r_fx > 0:
+            raise ValueError('link metrics are not covered on a column shard')
+        if not np.all(np.isfinite(self._b_host)):
+            raise ValueError('b must be finite (no NaN or inf)')
+        e = (dev_metrics.edges_check(edges) if edges is not None
+             else dev_metrics.link_classes(self._b_host, nbins))
+        torch = _torch()
+        many = isinstance(z, (list, tuple))
+        if z is None:
+            if getattr(self, '_last_zbuf', None) is None:
+                raise ValueError('link_metrics(z=None) reads the z of the last solve(): '
+                                 'there was none')
+            z = self.current_z(self._last_zbuf)
+        zs = list(z) if many else [z]
+        if not zs:
+            raise ValueError('link_metrics needs at least one state')
+        ax = torch.empty(len(zs), self.m, dtype=torch.float64, device='cuda')
+        for s, zi in enumerate(zs):
+            zi = torch.as_tensor(zi, dtype=torch.float64).cuda().reshape(-1)
+            if zi.numel() != self.nz:
+                raise ValueError('z has %d entries, expected %d' % (zi.numel(), self.nz))
+            if self._x0_own is None:
+                xh = self.n_apply(zi, with_x0=True)
+            else:
+                xh = self.n_apply(zi) + self._x0_own
+            ax[s].copy_(self.apply_A_x(xh))
+        cells = dev_metrics.launch(ax, self.m, self.b, self.row_weights, 0, e, self.m, len(zs))
+        return dev_metrics.metrics_from_cells(cells if many else cells[0])
 
     def _unweighted_only(self, what):
         if self.row_weights is not None:
@@ -973,6 +1024,7 @@ class BBEngine:
         (zb, _), = poll_solve(self, 1, self.P.max_iter, record_every, poll,
                               lambda j, i, s, d: log(i, s, d), first=lambda j: keep(self.z0),
                               state=lambda j, zb: keep(self.current_z(zb)), stopped=stopped)
+        self._last_zbuf = int(zb)
         return self.current_z(zb)
 
     def run_fixed(self, iters):

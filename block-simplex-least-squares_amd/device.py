@@ -17,6 +17,7 @@ sequences calls.  This module is its public face; the code lives in
   dev_lsq     the x-space operator pair and XBBEngine
   dev_bb      BBEngine, its option checks, the line search, the BB host loop
   dev_batch   BatchBB
+  dev_metrics the link metrics of a fit by set and flow class (GEH, RMSE, ..)
 Importing it needs neither a GPU nor torch.
 """
 from dev_images import (NT_BYTES, DeviceCSR, DevicePanels, DeviceTiles, PanelOverflow,
@@ -28,3 +29,4 @@ from dev_lsq import DeviceLSQ, XBBEngine, lsq_operator
 from dev_bb import (BBEngine, LineSearch, fixed_plan_fits, fixed_sum_bounds, fixed_sums_check,
                     reg_lambda_check, reg_model, reg_weights_check, row_weights_check)
 from dev_batch import BatchBB, _batch_columns, batch_groups, batch_width
+from dev_metrics import KEYS, link_classes, link_metrics, metrics_from_cells

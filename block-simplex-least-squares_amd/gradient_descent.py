@@ -28,8 +28,9 @@ from bsls_utils import lsv_operator
 class GradientDescent:
 
     def __init__(self, z0=None, f=None, nabla_f=None, proj=None, method='BB', options=None,
-                 A=None, N=None, target=None, engine=None, to_host=True):
+                 A=None, N=None, target=None, engine=None, to_host=True, record_every=None):
         self.z0 = z0
+        self.record_every = record_every                # BB only; None: BB.solve's 500
         self.f = f
         self.nabla_f = nabla_f
         self.proj = proj
@@ -76,13 +77,14 @@ class GradientDescent:
                         options=self.options)
             logging.debug('Took %s time' % str(np.sum(self.times)))
         elif self.method == 'BB':
+            every = {} if self.record_every is None else {'record_every': int(self.record_every)}
             if e is not None:
                 e.P.max_iter = int(self.options.get('max_iter', 300000))
                 e.P.opt_tol = float(self.options.get('opt_tol', 1e-6))
-                BB.solve_engine(e, z0=self.z0, log=self.log, to_host=self.to_host)
+                BB.solve_engine(e, z0=self.z0, log=self.log, to_host=self.to_host, **every)
             else:
                 BB.solve(self.z0, self.f, self.nabla_f, solvers.stopping, log=self.log,
-                         proj=self.proj, options=self.options)
+                         proj=self.proj, options=self.options, **every)
         elif self.method == 'DORE':
             if e is None:
                 if self.A is None or self.N is None or self.target is None:

@@ -50,6 +50,14 @@ def parser():
     p.add_argument('--cv-batch', dest='cv_batch', type=int, default=None, metavar='R',
                    help='with --cv: run the folds R (1..8) at a time in lockstep on one batched '
                         'engine (device.BatchBB) instead of one after another')
+    p.add_argument('--cv-metrics', dest='cv_metrics', action='store_true', default=False,
+                   help='with --cv (and with --cv-batch too): each fold\'s GEH / RMSE link '
+                        'metrics over its train and held-out links and per link class by flow '
+                        '(CrossValidation.py:186-274), reduced on the device: '
+                        'output[\'cv\'][i][\'train\' | \'test\' | \'train_bin\' | \'test_bin\']')
+    p.add_argument('--cv-bins', dest='cv_bins', type=int, default=6, metavar='N',
+                   help='with --cv-metrics: the number of link classes by flow (default 6, as '
+                        'the reference; 1..14)')
     p.add_argument('--reg', dest='reg', type=float, default=None, metavar='LAMBDA',
                    help='the reference\'s L2 regulariser, + 0.5 LAMBDA ||N z + x0||^2 '
                         '(CrossValidation.py:145-148, ISTTT.py:88-92; method BB only; per-route '
@@ -185,14 +193,14 @@ def host_closures(A, N, target, x0, row_weights=None, reg_lambda=0.0, reg_weight
 
 
 def solve_in_z_cpu(A, b, x0, N, block_sizes, method, options=None, row_weights=None,
-                   reg_lambda=0.0, reg_weights=None):
+                   reg_lambda=0.0, reg_weights=None, record_every=None):
     """python/main.py:41-79 on the host (BASELINE configs[0]): the reference's
     closures over SciPy csr_matvec, proj = the host c_extensions library's
     isotonic_regression_multi (include/bsls_cpu.h) + clip, the solver loops of
     BB.py / LBFGS.py / DORE.py over them.  row_weights w (BB only): the
     engine's weighted objective, f = 0.5 sum w r^2, nabla_f = N'A'(w r).
     reg_lambda / reg_weights (BB only): the reference's regularised closures
-    (host_closures)."""
+    (host_closures).  record_every (BB only): BB.solve's, None for its 500."""
     from bsls_utils import particular_x0
     from c_extensions import _cpu
     from device import reg_lambda_check
@@ -215,7 +223,7 @@ def solve_in_z_cpu(A, b, x0, N, block_sizes, method, options=None, row_weights=N
         return np.maximum(np.minimum(x, 1.), 0.)
     kw = dict(A=A, N=N, target=target) if method == 'DORE' else {}
     gd = GradientDescent(z0=z0, f=f, nabla_f=nabla_f, proj=proj, method=method, options=options,
-                         **kw)
+                         record_every=record_every, **kw)
     iters, times, states = gd.run()
     x = particular_x0(block_sizes) + N.dot(states[-1])
     assert np.all(x >= 0), "x shouldn't have negative entries after projection"
@@ -352,6 +360,12 @@ def main(args=None, plot=False):
         raise ValueError('--cv-batch needs --cv')
     if cv_batch is not None and not 1 <= cv_batch <= 8:
         raise ValueError('--cv-batch takes 1..8 (got %r)' % (cv_batch,))
+    cv_metrics = bool(getattr(args, 'cv_metrics', False))
+    cv_bins = getattr(args, 'cv_bins', 6)
+    if cv_metrics and cv is None:
+        raise ValueError('--cv-metrics needs --cv')
+    if cv_metrics and not 1 <= cv_bins <= 14:
+        raise ValueError('--cv-bins takes 1..14 (got %r)' % (cv_bins,))
     if args.log in ACCEPTED_LOG_LEVELS:
         logging.basicConfig(level=getattr(logging, args.log))
     config = {'full': True, 'L': True, 'OD': True, 'CP': True, 'LP': True,
@@ -382,7 +396,7 @@ def main(args=None, plot=False):
         if cv is not None:
             from cross_validation import kfold
             output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, device='cpu', batch=cv_batch,
-                                 reg_lambda=reg or 0.0)
+                                 reg_lambda=reg or 0.0, metrics=cv_metrics, nbins=cv_bins)
         return iters, times, states, output
     eng = build_engine(AA, bb, x0, block_sizes,
                        deterministic=getattr(args, 'deterministic', None),
@@ -394,7 +408,7 @@ def main(args=None, plot=False):
     if cv is not None:
         from cross_validation import kfold
         output['cv'] = kfold(AA, bb, x0, N, block_sizes, cv, engine=eng, batch=cv_batch,
-                             reg_lambda=reg or 0.0)
+                             reg_lambda=reg or 0.0, metrics=cv_metrics, nbins=cv_bins)
     if plot:
         import matplotlib.pyplot as plt
         plt.figure(); plt.hist(x_last)

@@ -1051,6 +1051,41 @@ int bsls_bbm_iterate(const bsls_bbm_problem *p, int64_t first_iter, int64_t coun
  * write z[iter & 1] / g[iter & 1]; stage 3 at iter <= 0 writes g[0]. */
 int bsls_bbm_stage(const bsls_bbm_problem *p, int stage, int64_t iter, void *stream);
 
+/* ---- link metrics of a fit, by set and flow class ---------------------------
+ * CrossValidation.post_process's metrics() (python/CrossValidation.py:193-214)
+ * for the train and the held-out links, and again per link class by flow
+ * (:246-274), as one table of sums the host divides (dev_metrics.py).
+ * ax: nstates vectors of A x_hat, state s at ax + s * ax_ld (ax_ld >= m); b: m,
+ * shared.  roww: NULL (every row is train), or a mask: roww_ld == 0 one for all
+ * states, roww_ld >= m state s's at roww + s * roww_ld; set 0 (train) is
+ * w != 0, set 1 (held out) w == 0.  edges: nedges (0..BSLS_LM_MAX_EDGES)
+ * non-decreasing doubles; row i's class is the number of edges e with
+ * e <= b_i (np.digitize(b, edges)).  Per row, in this order and uncontracted:
+ *   diff = ax - b; plus = ax + b; d2 = diff * diff; geh = sqrt((2.0 * d2) / plus)
+ * (np.sqrt(2 * diff**2 / plus), bit for bit; NaN and inf as NumPy gives them).
+ * out: nstates x 2 x (nedges + 1) x BSLS_LM_NV doubles, [state][set][class]
+ * [value]: the count, sum d2, sum geh, max geh (NaN-propagating), the counts of
+ * geh < 5 / 1 / 0.5 / 0.05 (strict; false for NaN) and sum b.  Counts are
+ * doubles holding integers; an empty cell is nine +0.0.  A row reaches its own
+ * cell only (selected, never multiplied by 0), so a NaN stays in its cell.
+ * Sums run in a fixed order (32 rows in row order, 16 such runs, then the
+ * workgroups' tables in up to 8 ranges in index order), without atomics: two
+ * launches give the same bits, and state s of a launch the bits of a
+ * one-state launch on its vector and mask.  work: bsls_link_metrics_work_size
+ * bytes, written in full before it is read (no zeroing needed).  Nothing but
+ * out and work is written.  BSLS_E_ARG: m < 1, nstates outside 1..1024, nedges
+ * outside 0..15, ax_ld < m, roww_ld neither 0 nor >= m, a NULL ax, b, out or
+ * work, NULL edges with nedges > 0. */
+enum { BSLS_LM_COUNT, BSLS_LM_SSQ, BSLS_LM_SUM_GEH, BSLS_LM_MAX_GEH,
+       BSLS_LM_UNDER_5, BSLS_LM_UNDER_1, BSLS_LM_UNDER_0_5, BSLS_LM_UNDER_0_05,
+       BSLS_LM_SUM_B, BSLS_LM_NV /* 9 */ };
+#define BSLS_LM_MAX_EDGES 15
+size_t bsls_link_metrics_work_size(int64_t m, int nstates, int nedges);
+int bsls_link_metrics(const double *ax, int64_t ax_ld, const double *b,
+                      const double *roww, int64_t roww_ld,
+                      const double *edges, int nedges,
+                      int64_t m, int nstates, double *out, void *work, void *stream);
+
 /* Library / device info (for the loader's self-check). */
 const char *bsls_version(void);
 int bsls_device_arch(char *buf, int buflen);
