@@ -1,7 +1,7 @@
 // shard.hip -- the column-sharded BB iteration of one rank, enqueued from C++
 // with its RCCL collectives in the same loop (include/bsls_hip.h
 // bsls_bb_shard_iterate).  The schedule is distributed.ShardedBB's (python),
-// the orchestration the gloo tests pin against the oracle (fuse 2, default):
+// the orchestration the gloo tests pin against the oracle:
 //     stage 10  K2 (g_g, the four local BB sums) + this rank's 1/world slice
 //               of ||r||^2 (r is the same all-reduced vector on every rank)
 //     RCCL      all-reduce(sum) of scal[SUMDG..RR]        40 B
@@ -10,10 +10,7 @@
 //               (atomic K1) r set to target / 0 for the next stage
 //     stage 14  K1: r_g = A_g x_g (+ target on the shard_role 1 rank)
 //     RCCL      all-reduce(sum) of r                      8 m B
-// and stage 9 (f / stop test) after the last iteration of a call; fuse 1
-// reads all of r for ||r||^2 in K2 (stage 8: the f of i - 1 in its last
-// workgroup, 14 us of an 8-way C5 rank's iteration for the 8 MB), fuse 0 runs
-// stage 3 and a stage 9 per iteration.  A Python
+// and stage 9 (f / stop test) after the last iteration of a call.  A Python
 // loop enqueued the same thing at ~4 ctypes calls + 2 torch.distributed calls
 // per iteration (tens of us of host time against a ~100-us device iteration
 // on 8 ranks); here an iteration costs 4 kernel launches + 2 RCCL calls of host
@@ -219,8 +216,8 @@ extern "C" int bsls_comm_all_reduce(bsls_comm *c, double *buf, int64_t count, vo
 }
 
 extern "C" int bsls_bb_shard_iterate(const bsls_bb_problem *p, bsls_comm *c, int64_t first_iter,
-                                     int64_t count, int fuse, void *stream) {
-    if (!p || !c || first_iter < 1 || count < 0 || fuse < 0 || fuse > 2) return BSLS_E_ARG;
+                                     int64_t count, void *stream) {
+    if (!p || !c || first_iter < 1 || count < 0) return BSLS_E_ARG;
     if (p->shard_role != (c->rank == 0 ? 1 : 2)) return BSLS_E_ARG;   // target added once
     // fixed-point row sums, row weights: one GCD only
     if (p->fx_sums || p->roww || p->reg_w) return BSLS_E_ARG;
@@ -235,33 +232,21 @@ extern "C" int bsls_bb_shard_iterate(const bsls_bb_problem *p, bsls_comm *c, int
     };
     int rc;
     for (int64_t i = first_iter; i < first_iter + count; ++i) {
-        if (fuse == 2) {
-            // K2 with this rank's slice of ||r||^2, the five sums over ranks,
-            // then f and the stop test of i - 1
-            // (K3_RECORD: K3 with RECORD -- f and the stop test of i - 1 --
-            // folded in)
-            // (K3_RECORD_INIT: that with the next K1's r initialisation folded
-            // in when K1 adds its group sums by atomics; K1_PARTIAL_INITED is
-            // then K1_PARTIAL without it)
-            if ((rc = bsls_bb_stage(p, BSLS_STAGE_K2_RR_SLICE, i, stream)) != BSLS_OK) return rc;
-            if ((rc = all_reduce(p->scal + BSLS_S_SUMDG, 5)) != BSLS_OK) return rc;
-            if ((rc = bsls_bb_stage(p, BSLS_STAGE_K3_RECORD_INIT, i, stream)) != BSLS_OK) return rc;
-        } else {
-            // K2 (+ the fused f / stop test of i - 1), then the BB sums over ranks
-            const int k2 = fuse ? BSLS_STAGE_K2_R_FINISH : BSLS_STAGE_K2;
-            if ((rc = bsls_bb_stage(p, k2, i, stream)) != BSLS_OK) return rc;
-            if ((rc = all_reduce(p->scal + BSLS_S_SUMDG, 4)) != BSLS_OK) return rc;
-            if ((rc = bsls_bb_stage(p, BSLS_STAGE_K3, i, stream)) != BSLS_OK) return rc;
-        }
+        // K2 with this rank's slice of ||r||^2, the five sums over ranks,
+        // then K3 with f and the stop test of i - 1
+        // (K3_RECORD_INIT: K3_RECORD with the next K1's r initialisation
+        // folded in when K1 adds its group sums by atomics; K1_PARTIAL_INITED
+        // is then K1_PARTIAL without it)
+        if ((rc = bsls_bb_stage(p, BSLS_STAGE_K2_RR_SLICE, i, stream)) != BSLS_OK) return rc;
+        if ((rc = all_reduce(p->scal + BSLS_S_SUMDG, 5)) != BSLS_OK) return rc;
+        if ((rc = bsls_bb_stage(p, BSLS_STAGE_K3_RECORD_INIT, i, stream)) != BSLS_OK) return rc;
         // the partial residual, then r = the sum over ranks (the one real exchange)
-        const int k1 = fuse == 2 ? BSLS_STAGE_K1_PARTIAL_INITED : BSLS_STAGE_K1_PARTIAL;
-        if ((rc = bsls_bb_stage(p, k1, i, stream)) != BSLS_OK) return rc;
+        if ((rc = bsls_bb_stage(p, BSLS_STAGE_K1_PARTIAL_INITED, i, stream)) != BSLS_OK) return rc;
         if (comm && (rc = comm_sum(c, p->r, (size_t)p->m, st, p->r_fx > 0.0)) != BSLS_OK)
             return rc;
-        if (!fuse && (rc = bsls_bb_stage(p, BSLS_STAGE_R_FINISH, i, stream)) != BSLS_OK) return rc;
     }
-    if (count > 0 && fuse)
-        return bsls_bb_stage(p, BSLS_STAGE_R_FINISH, first_iter + count - 1, stream);
+    // f and the stop test of the last iteration (every earlier one: the next K3's)
+    if (count > 0) return bsls_bb_stage(p, BSLS_STAGE_R_FINISH, first_iter + count - 1, stream);
     return BSLS_OK;
 }
 

@@ -102,13 +102,12 @@ class ShardedBB:
     soon as part p is enqueued its rows of r are all-reduced asynchronously
     (RCCL on its own stream, ordered after part p only), so the exchange of
     part p overlaps the computation of part p + 1; the compute stream waits
-    for every part before stage 2."""
+    for every part before the next stage."""
 
-    SUMS = slice(5, 9)      # scal[SUMDG..GG]
     SUMS_RR = slice(5, 10)  # scal[SUMDG..RR]
 
     def __init__(self, engine, all_reduce, parts=1, all_reduce_async=None, rank=None,
-                 fuse=None, native=None, slices=None):
+                 native=None, slices=None):
         if getattr(engine, 'row_weights', None) is not None:
             raise ValueError('a column shard is not covered by row_weights: '
                              'set_row_weights(None) first')
@@ -129,25 +128,14 @@ class ShardedBB:
         # iteration); row parts without link parts stay Python-driven
         self.native = native if (native is not None and (int(parts) <= 1 or self.link)) else None
         self._cstream = None
-        # fuse 2 (default): K2 sums this rank's slice of ||r||^2 beside the BB
-        # sums (stage 10), all-reduced with them, then f / stopping test
-        # (stage 12); 1: K2 reads all of r for it and tests in its last
-        # workgroup (stage 8); 0: stage 3 and a stage-9 launch after every
-        # residual exchange.  BSLS_SHARD_FUSE=0|1|2 (A/B).
-        if fuse is None:
-            fuse = int(os.environ.get('BSLS_SHARD_FUSE', '2'))
-        self.fuse = int(fuse)
-        if self.fuse not in (0, 1, 2):
-            raise ValueError('fuse must be 0, 1 or 2')
-        if self.fuse == 2:
-            # rows [lo, hi) of r: this rank's share of ||r||^2.  slices: the
-            # rank count (the process group's); a one-GPU rehearsal of rank 0
-            # of N passes N (its ||r||^2 is then 1/N of the true one: timing
-            # only)
-            if slices is None:
-                slices = _world_size()
-            m = engine.r.shape[0]
-            engine.set_rr_slice(rank * m // slices, (rank + 1) * m // slices)
+        # rows [lo, hi) of r: this rank's share of ||r||^2, which K2 sums
+        # beside the BB sums (stage 10).  slices: the rank count (the process
+        # group's); a one-GPU rehearsal of rank 0 of N passes N (its ||r||^2
+        # is then 1/N of the true one: timing only)
+        if slices is None:
+            slices = _world_size()
+        m = engine.r.shape[0]
+        engine.set_rr_slice(rank * m // slices, (rank + 1) * m // slices)
         # rank 0 adds target to its partial residual; the others zero theirs
         # once the run has stopped (bsls_bb_problem.shard_role)
         engine.set_shard_role(1 if rank == 0 else 2)
@@ -159,8 +147,6 @@ class ShardedBB:
             # (the link pipeline needs its exchanges asynchronous: from Python
             # through all_reduce_async, or the native driver's comm stream)
             raise ValueError('link parts need all_reduce_async or a native communicator')
-        if self.link and self.fuse != 2:
-            raise ValueError('link parts run the sliced schedule (fuse 2)')
         self._slices = None
         self._works = []
         if self.parts > 1:
@@ -175,12 +161,12 @@ class ShardedBB:
         return getattr(self.e, 'r_exchange', self.e.r)
 
     def residual(self, it):
-        """r = sum over ranks of A_g x_g (before stage 2)."""
+        """r = sum over ranks of A_g x_g (+ target, rank 0's)."""
         e = self.e
         if not self._slices or self.all_reduce_async is None:
             # (K1_PARTIAL_INITED: K1 after K3_RECORD_INIT, which may have initialised r)
-            e.stage(_native.STAGE_K1_PARTIAL_INITED if (self.fuse == 2 and it > 0)
-                    else _native.STAGE_K1_PARTIAL, it)
+            # (the prologue: K1_PARTIAL)
+            e.stage(_native.STAGE_K1_PARTIAL_INITED if it > 0 else _native.STAGE_K1_PARTIAL, it)
             self.all_reduce(self._rx())
             return
         works = []
@@ -200,7 +186,9 @@ class ShardedBB:
         engine can take it (fixed_r_ok depends on the rank's own shard: its K1
         plan, its formats), else every rank keeps doubles; ranks that decided
         alone would skip the others' all-reduces, or sum int64 words into
-        doubles.  BSLS_SHARD_RFX=0 keeps r in doubles.
+        doubles.  The ranks are those self.all_reduce spans (a subgroup's, not
+        the default group's): their count is all-reduced beside the choice.
+        BSLS_SHARD_RFX=0 keeps r in doubles.
 
         Precision: one scale for all rows resolves every row to 2^-61 B
         absolute; a row far below the largest bound carries more rounding than
@@ -217,20 +205,21 @@ class ShardedBB:
         ok = (os.environ.get('BSLS_SHARD_RFX', '1') != '0' and hasattr(e, 'fixed_r_ok')
               and bool(e.fixed_r_ok()))
         dev = getattr(e.r, 'device', 'cpu')
-        world = max(1, _world_size())
-        flag = torch.tensor([1.0 if ok else 0.0], dtype=torch.float64, device=dev)
-        if world > 1:
-            self.all_reduce(flag)
-        if float(flag.item()) != float(world):
+        # [ranks that can, ranks]: over the ranks self.all_reduce spans
+        flag = torch.tensor([1.0 if ok else 0.0, 1.0], dtype=torch.float64, device=dev)
+        self.all_reduce(flag)
+        can, world = (int(round(v)) for v in flag.tolist())
+        if can != world:
             return
         import math
         A = e._A_host
         S = np.asarray(abs(A).sum(axis=1)).ravel()
         t = torch.from_numpy(S).to(e.r.device)
         self.all_reduce(t)
-        world, rank = max(1, _world_size()), self._rank
+        # max|z0| over the ranks: one slot each, summed
         zv = torch.zeros(world, dtype=torch.float64, device=e.r.device)
-        zv[rank % world] = float(e.z0.abs().max()) if e.z0 is not None and e.z0.numel() else 0.0
+        if e.z0 is not None and e.z0.numel():
+            zv[self._rank % world] = float(e.z0.abs().max())
         self.all_reduce(zv)
         nzb = 2.0 * (float(zv.max()) + 1.0)
         B = float((e.target.abs() + nzb * t).max()) if t.numel() else 0.0
@@ -263,8 +252,7 @@ class ShardedBB:
                     ctypes.c_void_p(self._cstream.cuda_stream), stream_handle())
             elif count > 0:
                 rc = _native.lib().bsls_bb_shard_iterate(e.P, self.native.handle, int(first),
-                                                         int(count), int(self.fuse),
-                                                         stream_handle())
+                                                         int(count), stream_handle())
             if count > 0:
                 err = getattr(self.native, 'error', None)
                 if rc != 0 and err is not None:
@@ -275,25 +263,17 @@ class ShardedBB:
             self._iterate_link(first, count)
             return
         for i in range(first, first + count):
-            if self.fuse == 2:
-                e.stage(_native.STAGE_K2_RR_SLICE, i)   # K2 + this rank's slice of ||r||^2
-                self.all_reduce(e.scal[self.SUMS_RR])
-                # K3 after f / the stopping test of iteration i - 1;
-                # K3_RECORD_INIT also sets r to target / 0 for
-                # K1_PARTIAL_INITED's atomic K1 where the library folds that in
-                # (what bsls_bb_shard_iterate enqueues); row parts keep
-                # K3_RECORD (each part initialises its rows)
-                e.stage(_native.STAGE_K3_RECORD if self._slices
-                        else _native.STAGE_K3_RECORD_INIT, i)
-            else:
-                # (K2_R_FINISH: + f / stop test of i - 1)
-                e.stage(_native.STAGE_K2_R_FINISH if self.fuse else _native.STAGE_K2, i)
-                self.all_reduce(e.scal[self.SUMS])
-                e.stage(_native.STAGE_K3, i)
+            e.stage(_native.STAGE_K2_RR_SLICE, i)   # K2 + this rank's slice of ||r||^2
+            self.all_reduce(e.scal[self.SUMS_RR])
+            # K3 after f / the stopping test of iteration i - 1;
+            # K3_RECORD_INIT also sets r to target / 0 for
+            # K1_PARTIAL_INITED's atomic K1 where the library folds that in
+            # (what bsls_bb_shard_iterate enqueues); row parts keep
+            # K3_RECORD (each part initialises its rows)
+            e.stage(_native.STAGE_K3_RECORD if self._slices
+                    else _native.STAGE_K3_RECORD_INIT, i)
             self.residual(i)
-            if not self.fuse:
-                e.stage(_native.STAGE_R_FINISH, i)    # f / stopping test of iteration i
-        if count > 0 and self.fuse:
+        if count > 0:
             # f / stopping test of the last one
             e.stage(_native.STAGE_R_FINISH, first + count - 1)
 

@@ -369,7 +369,7 @@ typedef struct bsls_bb_problem {
     /* Tile images replacing the panels when their ent is not NULL (then A / AT
      * are not read): At for K1 (halo 0; ngroups partials in rpart), ATt for K2
      * (halo 1; with ngroups > 1 the partial row sums go through wpart,
-     * ngroups * nrb * (H + 1) doubles, then ngroups * nrb slots for stage 8's
+     * ngroups * nrb * (H + 1) doubles, then ngroups * nrb slots for stage 8 / 10's
      * r^2 slices: ngroups * nrb * (H + 2) doubles in all). */
     bsls_tiles At;
     bsls_tiles ATt;
@@ -582,14 +582,15 @@ enum bsls_stage {
      * BSLS_STAGE_K3_RECORD */
     BSLS_STAGE_K3_RECORD_INIT = 15
 };
-/* One iteration i >= 1 = 3, [allreduce sums], 4, 1, [allreduce r], 2; on one GCD
- * bsls_bb_iterate runs 3, 4, 7 (with reg_w: 3, 4, bsls_bb_reg on z[i & 1], 7;
- * python/CrossValidation.py:141-144).  The column-sharded driver (distributed.py,
- * shard_role 1 / 2) runs 8, [allreduce sums], 4, 1, [allreduce r] per
- * iteration and 9 after the last one (fuse 1), or the sliced form 10,
- * [allreduce 5 sums], 15, 14, [allreduce r] (fuse 2, the default; both the
- * native driver bsls_bb_shard_iterate and the Python loop; 13 and 1 where K1
- * runs in row parts, bsls_bb_residual_rows).  After a stop, stage 3 / 8 / 10
+/* On one GCD bsls_bb_iterate runs 3, 4, 7 per iteration i >= 1 (with reg_w:
+ * 3, 4, bsls_bb_reg on z[i & 1], 7; python/CrossValidation.py:141-144).  The
+ * column-sharded driver (distributed.py, shard_role 1 / 2) runs 10,
+ * [allreduce 5 sums], 15, 14, [allreduce r] per iteration and 9 after the
+ * last one (both the native driver bsls_bb_shard_iterate and the Python loop;
+ * 13 and 1 where K1 runs in row parts, bsls_bb_residual_rows).  No driver
+ * enqueues 2, 8 or 12 any more; they and 3, 4, 1 and 9 stay, so a caller can
+ * still enqueue the unfused sequences (3 or 8, [allreduce 4 sums], 4, 1,
+ * [allreduce r], 9) by hand.  After a stop, stage 3 / 8 / 10
  * on a shard_role 2 rank zero its scal[SUMDG..RR], so the all-reduces the
  * driver still enqueues keep the stop iteration's sums (role 1's copy). */
 int bsls_bb_stage(const bsls_bb_problem *p, int stage, int64_t iter, void *stream);
@@ -689,17 +690,15 @@ int bsls_comm_create_callback(int world, int rank, bsls_all_reduce_fn fn, void *
 int bsls_comm_force_collectives(bsls_comm *comm, int on);
 /* in-place sum of `count` doubles over the ranks, on `stream` */
 int bsls_comm_all_reduce(bsls_comm *comm, double *d_buf, int64_t count, void *stream);
-/* Iterations first_iter .. first_iter+count-1 of the sharded schedule (fuse 2:
- * per iteration stage 10, all-reduce scal[SUMDG..RR], stage 15, stage 14,
- * all-reduce r; fuse 1: stage 8, all-reduce scal[SUMDG..GG], 4, 1,
- * all-reduce r; fuse 0: stage 3 instead of 8 and a stage 9 after every r
- * exchange; stage 9 after the last iteration in all three).  p->shard_role
+/* Iterations first_iter .. first_iter+count-1 of the sharded schedule: per
+ * iteration stage 10, all-reduce scal[SUMDG..RR], stage 15, stage 14,
+ * all-reduce r; stage 9 after the last iteration.  p->shard_role
  * must be 1 on rank 0 and 2 elsewhere (target added once).  A one-rank
  * communicator skips the collectives (a sum over one rank) unless
  * bsls_comm_force_collectives turned them on.  All on
  * `stream`; nothing waits on the host. */
 int bsls_bb_shard_iterate(const bsls_bb_problem *p, bsls_comm *comm, int64_t first_iter,
-                          int64_t count, int fuse, void *stream);
+                          int64_t count, void *stream);
 
 /* ---- the exchange pipelined behind the walks (link parts) -------------------
  * The K2 image holds `nparts` column groups whose link ranges

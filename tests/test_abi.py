@@ -107,6 +107,24 @@ def test_stage_ids_match_header(native, tmp_path):
     assert sorted(c_ids.values()) == list(range(11)) + list(range(12, 16))
 
 
+def test_shard_iterate_takes_five_arguments(native):
+    """bsls_bb_shard_iterate(p, comm, first_iter, count, stream): the header's
+    prototype and _native's argtypes agree on the five, and the export refuses
+    a NULL problem before anything else."""
+    import re
+    hdr = open(os.path.join(ROOT, 'include', 'bsls_hip.h')).read()
+    proto = re.search(r'int bsls_bb_shard_iterate\(([^)]*)\);', hdr).group(1)
+    params = [' '.join(a.split()) for a in proto.split(',')]
+    assert params == ['const bsls_bb_problem *p', 'bsls_comm *comm', 'int64_t first_iter',
+                      'int64_t count', 'void *stream']
+    L = native.load()
+    fn = L.bsls_bb_shard_iterate
+    assert fn.restype is ctypes.c_int
+    assert list(fn.argtypes) == [ctypes.POINTER(native.BBProblem), ctypes.c_void_p, ctypes.c_int64,
+                                 ctypes.c_int64, ctypes.c_void_p]
+    assert fn(None, None, 1, 0, None) == native.BSLS_E_ARG
+
+
 def test_panel_limits_match_header(native):
     hdr = open(os.path.join(ROOT, 'include', 'bsls_hip.h')).read()
     assert '#define BSLS_PANEL_CHUNK %d' % native.PANEL_CHUNK in hdr

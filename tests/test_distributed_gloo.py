@@ -3,7 +3,7 @@
 The GPU stages are replaced by a NumPy test double that implements each stage's
 contract from include/bsls_hip.h (bsls_bb_stage) with the oracle's PAVA, so
 what is tested is the sharding: block-aligned column split, the r all-reduce,
-the four-sum all-reduce and the stage order.  The sharded run must reproduce
+the five-sum all-reduce and the stage order.  The sharded run must reproduce
 the unsharded run and the oracle's BB trajectory (python/BB.py semantics).
 """
 import os
@@ -184,7 +184,7 @@ class FakeStages:
             if self.fold:
                 self._init_r()
             self.stage(4, it)
-        elif k in (3, 8, 10):
+        elif k in (3, 10):
             if it > 0 and float(s[0]) != 0:
                 self._stopped_sums(k)
                 return
@@ -195,11 +195,6 @@ class FakeStages:
             self.g[zn][:] = g
             dg = g - self.g[zc]
             dz = self.z[zc] - self.z[zn]
-            if k == 8:
-                self._record(it - 1)     # before this iteration's sums land
-                if float(s[0]) != 0:     # stopped at it - 1: its sums stay
-                    self._stopped_sums(k)
-                    return
             if k == 10:
                 s[11:15] = s[5:9].clone()            # iteration it - 1's sums, for stage 12
                 rs = self.r[self.rr_lo:self.rr_hi] if self.rr_hi > self.rr_lo else self.r
@@ -383,33 +378,6 @@ def test_two_rank_link_parts_match_single(orc, fold):
         assert np.max(np.abs(two[rank]['scal'][5:9] - s1)) <= 1e-9 * max(1.0, np.max(np.abs(s1)))
 
 
-@pytest.mark.timeout(600)
-def test_two_rank_unfused_schedule(orc, monkeypatch):
-    """The three schedules (BSLS_SHARD_FUSE=2, the default: stage 10's sliced
-    ||r||^2 all-reduced with the sums and stage 12's stop test; 1: stage 8's
-    fused test; 0: stage 3 and a stage-9 test after every exchange): the same
-    trajectory, and the same stop."""
-    iters = 10
-    fused = _spawn(2, iters)                    # the sliced schedule (fuse 2, default)
-    base = _spawn(2, 9, stop_at=5)
-    for rank in (0, 1):
-        assert base[rank]['scal'][0] == 2 and base[rank]['scal'][1] == 5
-    s5 = base[0]['scal'][5:9]
-    for mode in ('0', '1'):
-        monkeypatch.setenv('BSLS_SHARD_FUSE', mode)
-        plain = _spawn(2, iters)
-        for i in fused:
-            d = np.max(np.abs(fused[i] - plain[i])) / max(1.0, np.max(np.abs(fused[i])))
-            assert d < 1e-12, (mode, i, d)
-        two = _spawn(2, 9, stop_at=5)
-        for rank in (0, 1):
-            assert two[rank]['scal'][0] == 2 and two[rank]['scal'][1] == 5, mode
-            # the stopping iteration's sums stay in scal whatever the schedule
-            d = np.max(np.abs(two[rank]['scal'][5:9] - s5)) / max(1.0, np.max(np.abs(s5)))
-            assert d < 1e-9, (mode, rank, d)
-        monkeypatch.delenv('BSLS_SHARD_FUSE')
-
-
 def test_row_parts():
     sys.path.insert(0, PKG)
     from distributed import row_parts
@@ -464,17 +432,21 @@ class _FxEngine:
         self.scale = s
 
 
-def _fx_run(rank, world, port, q, oks):
+def _fx_run(rank, world, port, q, oks, sub=None):
+    """sub: the ranks of a subgroup that drv.all_reduce spans instead of the
+    default group; a rank outside it takes no part in the decision."""
     sys.path.insert(0, PKG)
     os.environ['MASTER_ADDR'] = '127.0.0.1'
     os.environ['MASTER_PORT'] = str(port)
     dist.init_process_group('gloo', rank=rank, world_size=world)
-    from distributed import ShardedBB
-    e = _FxEngine(rank, oks[rank])
-    drv = ShardedBB.__new__(ShardedBB)        # only the fixed-point decision
-    drv.e, drv._rank = e, rank
-    drv.all_reduce = lambda t: dist.all_reduce(t, op=dist.ReduceOp.SUM)
-    drv._fix_r()
+    from distributed import ShardedBB, torch_all_reduce
+    group = dist.new_group(list(sub)) if sub else None    # (collective: every rank)
+    e = _FxEngine(rank, oks[rank] if rank < len(oks) else False)
+    if sub is None or rank in sub:
+        drv = ShardedBB.__new__(ShardedBB)        # only the fixed-point decision
+        drv.e, drv._rank = e, rank
+        drv.all_reduce = torch_all_reduce(group)
+        drv._fix_r()
     # the ranks still agree on every later collective
     t = torch.ones(1, dtype=torch.float64)
     dist.all_reduce(t)
@@ -506,3 +478,27 @@ def test_fixed_point_r_is_a_collective_choice(oks):
         assert res[0][0] == res[1][0] == 2.0 ** 56
     else:
         assert res[0][0] is None and res[1][0] is None
+
+
+@pytest.mark.timeout(300)
+def test_fixed_point_r_choice_spans_the_all_reduce_group():
+    """the choice is counted over the ranks that drv.all_reduce
+    spans, not the default group's.  Ranks 0 and 1 of three form a subgroup
+    and both can take the fixed point: both choose it, at the scale of the
+    two-rank case above (the same two engines); rank 2 takes no part, and the
+    three still agree on a later world all-reduce.  (Compared with the default
+    group's size, 2 of 3 never matched and the scale stayed None.)"""
+    ctx = mp.get_context('spawn')
+    q = ctx.Queue()
+    port = 32000 + (os.getpid() % 900)
+    ps = [ctx.Process(target=_fx_run, args=(r, 3, port, q, (True, True), (0, 1)))
+          for r in range(3)]
+    for p in ps:
+        p.start()
+    res = {item[0]: item[1:] for item in (q.get(timeout=120) for _ in ps)}
+    for p in ps:
+        p.join(timeout=60)
+        assert p.exitcode == 0
+    assert res[0][1] == res[1][1] == res[2][1] == 3.0
+    assert res[0][0] is not None and res[0][0] == res[1][0] == 2.0 ** 56
+    assert res[2][0] is None

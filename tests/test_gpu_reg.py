@@ -669,7 +669,7 @@ def test_library_refusals(cuda):
     try:
         for role in (0, 1):
             P.shard_role = role
-            assert L.bsls_bb_shard_iterate(P, comm.handle, 1, 1, 2, st) == E
+            assert L.bsls_bb_shard_iterate(P, comm.handle, 1, 1, st) == E
             other = torch.cuda.Stream()
             lb = (ctypes.c_int64 * 3)(0, 1, 2)
             assert L.bsls_bb_shard_iterate_parts(P, comm.handle, 1, 1, 2, lb,

@@ -8,8 +8,9 @@ Both files come from the same unit compiled with the Makefile's FLAGS plus
 label to its `.Lfunc_end` label (its `.amdhsa_kernel ... .end_amdhsa_kernel`
 block lies in between) is compared as text.  The only thing set aside is the
 function's ordinal in the file, which the compiler writes into its local
-labels (`.LBB<n>_<k>`, `.Lfunc_end<n>`, `BB<n>_<k>` in its loop comments): a
-kernel that merely moved in the source keeps its text.  Prints the symbol
+labels (`.LBB<n>_<k>`, `.Lfunc_end<n>`, `BB<n>_<k>` in its loop comments),
+and with it the blanks that pad a label's comment to its column: a kernel
+that merely moved in the source keeps its text.  Prints the symbol
 counts and every name that is only on one side or differs; exit status 0 when
 every NEW symbol is in OLD with the same text and every OLD symbol is in NEW
 or named by --gone.
@@ -37,7 +38,10 @@ def kernels(path):
         # (the compiler writes the kernel's descriptor block before its end label)
         text = '\n'.join(lines[i:j + 1])
         assert '.amdhsa_kernel ' + name in text and '.end_amdhsa_kernel' in text, name
-        out[name] = re.sub(r'(\.L[A-Za-z_]+|\bBB)' + n + r'(?![0-9])', r'\1#', text)
+        text = re.sub(r'(\.L[A-Za-z_]+|\bBB)' + n + r'(?![0-9])', r'\1#', text)
+        # (a label's comment is padded to a column, so the ordinal's digit
+        # count -- 99 against 100 -- shows in the blanks before its `;`)
+        out[name] = re.sub(r'[ \t]+;', ' ;', text)
     return out
 
 
